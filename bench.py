@@ -16,6 +16,12 @@ frames into the same replay: ``--actor_envs`` envs x ``update_freq // envs``
 batched eps-greedy steps = update_freq (4) env frames per SGD step, the
 reference's 1:4 acting/learning ratio (`scripts/dqn_params.sh:38`).
 Prints ONE JSON line on rank 0; ``value`` = total SGD steps/s over all ranks.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line; the start-up probes it
+keeps (G = 1 vs G steps per graph launch, ~100 steps) choose the timed path, and the end-of-run
+replica / peer-wait checks are free on one GPU. ``--full`` is where anything beyond that belongs
+(nothing today). ``--dump-outputs DIR`` writes the last timed step's results as ``DIR/<name>.npy``;
+every input is seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -78,6 +84,37 @@ def timed_split(steps: int, g_max: int):
     return g_max, steps // g_max, steps % g_max
 
 
+DUMP_LIMIT = 64 << 20          # bytes --dump-outputs writes at most, over all arrays
+
+
+def dump_outputs(path: str, learner, net) -> dict:
+    """What the last timed step left its caller, as ``path/<name>.npy`` (float32; integers float64): the TD loss
+    ``Learner.step`` returns and the state it updated in place -- online and target parameters,
+    every optimizer slot, the device global_step. An array over its share of DUMP_LIMIT is written
+    as a fixed sample (sorted indices of a seed-0 permutation, the same in every run and build).
+    Returns {name: [elements written, elements]}."""
+    import re
+
+    import numpy as np
+    from dist_dqn_amd.parallel.dp import state_tensors
+    named = [('loss', learner.loss)] + [(n, t) for n, t in state_tensors(net)
+                                        if n in ('online', 'target', 'global_step') or n.startswith('slot/')]
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT // (4 * len(named))          # float32 elements per array
+    written = {}
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > share:
+            keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:share].sort().values
+            flat = flat.index_select(0, keep.to(flat.device))
+        arr = flat.to(torch.float32 if flat.is_floating_point() else torch.float64).cpu().numpy()
+        name = re.sub(r'[^A-Za-z0-9_.-]', '_', name)
+        np.save(os.path.join(path, name + '.npy'), arr)
+        written[name] = [int(arr.size), int(n)]
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -108,6 +145,12 @@ def main():
                     help='1 (one GPU only): run the data-parallel step at W = 1 -- a one-rank RCCL group with every '
                          'DP code path on (in-graph xgmi gather + in-launch gradient exchange): the per-rank cost of '
                          'the multi-GPU step without peers')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed step left its caller -- the TD loss, the '
+                         'online and target parameters, every optimizer slot -- as DIR/<name>.npy (float32; rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the measurements and checks a plain run leaves out (today none: a plain run '
+                         'already does only what the headline figure needs, so --full runs the same steps)')
     args = ap.parse_args()
     if args.dp_path and args.gpus != 1:
         ap.error('--dp_path is the one-rank probe of the DP step (--gpus 1)')
@@ -249,6 +292,7 @@ def main():
         dist.all_reduce(frames)
     frames = float(frames)
     loss = float(learner.loss)
+    dumped = dump_outputs(args.dump_outputs, learner, net) if args.dump_outputs and ctx.rank == 0 else None
     xgmi_ok = learner.reducer.xgmi.check() if learner.reducer.xgmi is not None else True
     # (outside the timed region) every replica tensor must still be bit-identical to rank 0's
     eq = check_state_equal(ctx, net)
@@ -277,7 +321,7 @@ def main():
                        'acting': 'fused into the learner launches' if fused else 'separate launches',
                        'update_freq': args.update_freq, 'replay_capacity': cfg.replay_memory_capacity,
                        'num_actions': args.actions, 'variant': args.variant, 'extra': args.extra,
-                       'final_loss': loss,
+                       'final_loss': loss, 'full': bool(args.full), 'dumped_outputs': dumped,
                        'allreduce': learner.reducer.mode if ctx.enabled else None,
                        'allreduce_probe_us': learner.reducer.timings or None,
                        'xgmi_vs_rccl_max_rel': (learner.reducer.timings or {}).get('xgmi_vs_rccl_max_rel'),

@@ -3,6 +3,7 @@
 processes / shared memory lifecycle, and end-to-end Ape-X training on the CPU."""
 import glob
 import os
+import platform
 import shutil
 import subprocess
 
@@ -14,6 +15,20 @@ from dist_dqn_amd.config import parse_args
 from dist_dqn_amd.native import load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _run_tsan(exe):
+    """Run a ThreadSanitizer binary, with address randomisation off for that one process where
+    `setarch -R` works. The runtime maps its shadow at fixed addresses; when the kernel randomises
+    mappings with more bits than that runtime knows (vm.mmap_rnd_bits 32 under gcc 11's) it dies at
+    start-up, before any of the program runs: 'unexpected memory mapping' (exit 66) or SIGSEGV."""
+    cmd = [exe]
+    if shutil.which('setarch'):
+        pre = ['setarch', platform.machine(), '-R']
+        if subprocess.run(pre + ['true'], capture_output=True).returncode == 0:
+            cmd = pre + cmd
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=600,
+                          env=dict(os.environ, TSAN_OPTIONS='halt_on_error=1'))
 
 
 def test_ring_roundtrip_and_backpressure():
@@ -59,8 +74,7 @@ def test_host_runtime_under_thread_sanitizer(tmp_path):
     if r.returncode != 0 and 'tsan' in (r.stderr + r.stdout).lower():
         pytest.skip('ThreadSanitizer runtime unavailable')
     assert r.returncode == 0, r.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, TSAN_OPTIONS='halt_on_error=1'))
+    run = _run_tsan(exe)
     assert run.returncode == 0, run.stdout + run.stderr
     assert 'ThreadSanitizer' not in run.stderr, run.stderr
     assert 'ring errors 0, mailbox errors 0' in run.stdout
@@ -79,8 +93,7 @@ def test_ingest_service_under_thread_sanitizer(tmp_path):
     if r.returncode != 0 and 'tsan' in (r.stderr + r.stdout).lower():
         pytest.skip('ThreadSanitizer runtime unavailable')
     assert r.returncode == 0, r.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, TSAN_OPTIONS='halt_on_error=1'))
+    run = _run_tsan(exe)
     assert run.returncode == 0, run.stdout + run.stderr
     assert 'ThreadSanitizer' not in run.stderr, run.stderr
     assert 'errors 0' in run.stdout, run.stdout
@@ -98,8 +111,7 @@ def test_inference_service_under_thread_sanitizer(tmp_path):
     if r.returncode != 0 and 'tsan' in (r.stderr + r.stdout).lower():
         pytest.skip('ThreadSanitizer runtime unavailable')
     assert r.returncode == 0, r.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, TSAN_OPTIONS='halt_on_error=1'))
+    run = _run_tsan(exe)
     assert run.returncode == 0, run.stdout + run.stderr
     assert 'ThreadSanitizer' not in run.stderr, run.stderr
     assert 'errors 0' in run.stdout, run.stdout

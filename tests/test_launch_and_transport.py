@@ -48,6 +48,39 @@ def test_timed_split_prefers_a_dividing_graph_size():
     assert bench.timed_split(64, 1) == (1, 0, 64)
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: the loss, both parameter sets, every optimizer slot and the step counter as
+    .npy (float32, the integer counter float64); an array over its share of the byte limit is a
+    fixed sample, the same indices in every call."""
+    import types
+
+    import numpy as np
+
+    import bench
+    from dist_dqn_amd.config import parse_args
+    from dist_dqn_amd.models.network import Network
+    cfg = parse_args(['--env=CartPole-v0', '--network=simple', '--optimizer=adam', '--device=cpu', '--seed=0'])
+    net = Network.create_network(cfg, (4,), 2)
+    net.global_step.fill_(7)
+    learner = types.SimpleNamespace(loss=torch.tensor([1.5]))
+    n = net.online.flat.numel()
+    w = bench.dump_outputs(str(tmp_path / 'a'), learner, net)
+    assert set(w) == {'loss', 'online', 'target', 'global_step', 'slot_Adam', 'slot_Adam_1'}
+    assert w['online'] == [n, n] and w['loss'] == [1, 1]
+    for name in w:
+        a = np.load(tmp_path / 'a' / (name + '.npy'))
+        assert a.dtype == (np.float64 if name == 'global_step' else np.float32) and a.size == w[name][0]
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'online.npy'), net.online.flat.numpy())
+    assert np.load(tmp_path / 'a' / 'loss.npy').item() == 1.5 and np.load(tmp_path / 'a' / 'global_step.npy').item() == 7
+    # a limit the parameter arrays exceed: 16 elements of each, at fixed sorted positions
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 6 * 4 * 16)
+    w = bench.dump_outputs(str(tmp_path / 'b'), learner, net)
+    assert w['online'] == [16, n] and w['loss'] == [1, 1]
+    keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:16].sort().values
+    np.testing.assert_array_equal(np.load(tmp_path / 'b' / 'online.npy'), net.online.flat[keep].numpy())
+    assert sum(os.path.getsize(tmp_path / 'b' / f) - 128 for f in os.listdir(tmp_path / 'b')) <= 6 * 4 * 16
+
+
 def test_bench_gpus_beyond_the_node_refuses_without_running():
     """No GPU here: --gpus 8 must exit non-zero with a message and print no JSON line."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '4'],

@@ -116,3 +116,42 @@ def test_production_step_matches_fp32_oracle_every_tensor(variant, acting, dtype
     # every tensor of the net (Nature: conv1..3, fcl, output / value + advantage streams; noisy: sigma too)
     assert len(checked) >= 10, checked
     assert any(n.startswith('conv1') for n in checked) and any('fcl' in n for n in checked)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` (one process, small replay): the line's
+    ``steps`` is N, ``ms_per_step`` is the timed region over N and agrees with ``value``, and DIR holds
+    the last step's loss, parameters and optimizer slots as finite float32 arrays within 64 MB. N + the
+    warm-up and probe steps all ran (global_step), the online net moved and the target did not follow
+    (hard sync every 10k steps)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'DQN_DIST_BACKEND')}
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '48', '--warmup', '20',
+           '--replay', '20000', '--dump-outputs', str(tmp_path / 'out')]
+    out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=200)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d['steps'] == 48 and d['warmup'] == 20 and d['n_gpus'] == 1 and d['higher_is_better'] is True
+    tl = d['config']['timed_launches']
+    assert tl['graph_launches_of_G'] * d['graph_steps'] + tl['single_step_graphs'] == 48
+    assert d['ms_per_step'] > 0 and d['value'] == pytest.approx(1000.0 / d['ms_per_step'], rel=5e-3)   # (both rounded: 1e-4 ms of >= 0.02 ms)
+    assert d['dtype'] == 'bf16' and d['unit'].startswith('SGD steps/s') and d['config']['full'] is False
+    arrs = {f[:-4]: np.load(tmp_path / 'out' / f) for f in sorted(os.listdir(tmp_path / 'out'))}
+    assert set(arrs) == {'loss', 'online', 'target', 'global_step', 'slot_RMSProp', 'slot_RMSProp_1'}
+    assert set(d['config']['dumped_outputs']) == set(arrs)
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    for name, a in arrs.items():
+        assert a.dtype == (np.float64 if name == 'global_step' else np.float32), name
+        assert np.isfinite(a).all(), name
+    assert arrs['loss'].item() == pytest.approx(d['config']['final_loss'], rel=1e-6)
+    assert arrs['global_step'].item() >= 48 + 20
+    assert arrs['online'].size == arrs['target'].size > 1000000
+    assert not np.array_equal(arrs['online'], arrs['target'])
