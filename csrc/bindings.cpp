@@ -313,13 +313,17 @@ void optim_pack(int64_t op, torch::Tensor w, torch::Tensor grad, torch::Tensor s
   float h[9];
   for (int i = 0; i < 9; ++i) h[i] = (float)hp[i];
   c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
-  launch_optim_pack((int)op, ptr<float>(w), ptr<float>(grad), ptr<float>(s0), ptr<float>(s1), ptr<float>(beta_pow),
+  const bool launched =
+      launch_optim_pack((int)op, ptr<float>(w), ptr<float>(grad), ptr<float>(s0), ptr<float>(s1), ptr<float>(beta_pow),
                     ptr<int64_t>(step), ptr<int32_t>(ticket), h, (float)lr, (float)reg, (int)reg_end,
                     (float)grad_scale, jobs.data_ptr(), (int)(jobs.numel() / upd_job_ints()), packed.data_ptr(), tgt,
                     tgtp, (int)target_freq, (int)max_grid, nz, ef, gnz, ndst, nn, sample.empty() ? nullptr : &smp,
                     per_p.empty() ? nullptr : &per, tnz, tef, tpkp, nrng, fc.empty() ? nullptr : &ff,
                     reinterpret_cast<const float*>(part), reinterpret_cast<const void*>(wg), (int)wg_blocks,
                     dp.empty() ? nullptr : &dpl, reinterpret_cast<void*>(tsg), no_pack ? 1 : 0, cur_stream());
+  TORCH_CHECK(launched, "optim_pack: the launcher refused these arguments and launched nothing: no kernel is built "
+              "for optimizer ", op, " with this combination of noise, target_noise, per, fc, wg and dp, or a wg / dp "
+              "argument failed the launcher's own check");
 }
 
 void noise_normal(torch::Tensor out0, c10::optional<torch::Tensor> out1, torch::Tensor rng) {

@@ -54,8 +54,10 @@ struct FcFuse {
   int M, ldx, ldh;
 };
 // dp: nullptr or a dqn::DpLaunch (WG launches under data parallelism: the dependent jobs exchange
-// their gradients with every rank inside the launch, see DpExchange below)
-void launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
+// their gradients with every rank inside the launch, see DpExchange below).
+// Returns false, with nothing enqueued, when the arguments select a launch this build does not
+// instantiate (optim_pack.h DQN_OPT_MODES) or fail the binding's own checks.
+bool launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
                        int32_t* ticket, const float* hp9, float lr, float reg, int reg_end, float grad_scale,
                        const void* jobs, int njobs, void* packed, float* tgt, void* tgt_packed, int tfreq, int max_grid,
                        const float* noise, float* eff, const float* gnoise, float* noise_dst, int noise_n,

@@ -148,7 +148,7 @@ void launch_optimizer_step(int op, float* w, const float* g, float* s0, float* s
   }
 }
 
-void launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
+bool launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
                        int32_t* ticket, const float* hp9, float lr, float reg, int reg_end, float grad_scale,
                        const void* jobs, int njobs, void* packed, float* tgt, void* tgt_packed, int tfreq,
                        int max_grid, const float* noise, float* eff, const float* gnoise, float* noise_dst,
@@ -172,12 +172,12 @@ void launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, f
   L.per = per != nullptr ? *per : PerStep{};
   // WG: the launch also computes the grouped weight gradients (tiles after the lead block)
   const bool wgm = wg != nullptr && ff.x != nullptr && op >= 0;
-  if (wg != nullptr && !wgm) return;      // (binding checks: a WG launch needs FcFuse rows and an update)
+  if (wg != nullptr && !wgm) return false;   // (binding checks: a WG launch needs FcFuse rows and an update)
   // DP (WG under data parallelism): the dependent jobs run in dp->blocks blocks
   const DpLaunch dpl = (wgm && dp != nullptr) ? *reinterpret_cast<const DpLaunch*>(dp) : DpLaunch{nullptr, 0, 0, 0};
   if (dp != nullptr && (dpl.x == nullptr || dpl.blocks < 1 || dpl.blocks > dpl.n || dpl.first < 0 ||
                         dpl.first + dpl.n > njobs || dpl.n > kDpxMaxSlots))
-    return;                               // (binding checks)
+    return false;                         // (binding checks)
   const int nblk_jobs = dpl.x != nullptr ? njobs - dpl.n + dpl.blocks : njobs;
   // + the lead block (sampler / closer) + the weight-gradient tiles
   L.grid = (nblk_jobs < cap ? nblk_jobs : cap) + (L.smp.size != nullptr || L.per.sum != nullptr || wgm ? 1 : 0) +
@@ -199,16 +199,16 @@ void launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, f
   L.part = part; L.wg = reinterpret_cast<const WgradGroup*>(wg); L.wg_blocks = wgm ? wg_blocks : 0;
   L.dp = dpl;
   switch (op) {
-    case -1: optim_pack_op<-1>(L); break;
-    case 0: optim_pack_op<0>(L); break;
-    case 1: optim_pack_op<1>(L); break;
-    case 2: optim_pack_op<2>(L); break;
-    case 3: optim_pack_op<3>(L); break;
-    case 4: optim_pack_op<4>(L); break;
-    case 5: optim_pack_op<5>(L); break;
-    case 6: optim_pack_op<6>(L); break;
-    case 7: optim_pack_op<7>(L); break;
-    default: break;
+    case -1: return optim_pack_op<-1>(L);
+    case 0: return optim_pack_op<0>(L);
+    case 1: return optim_pack_op<1>(L);
+    case 2: return optim_pack_op<2>(L);
+    case 3: return optim_pack_op<3>(L);
+    case 4: return optim_pack_op<4>(L);
+    case 5: return optim_pack_op<5>(L);
+    case 6: return optim_pack_op<6>(L);
+    case 7: return optim_pack_op<7>(L);
+    default: return false;
   }
 }
 

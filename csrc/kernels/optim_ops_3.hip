@@ -4,5 +4,5 @@
 #include "optim_pack.h"
 
 namespace dqn {
-template void optim_pack_op<3>(const OptPackLaunch&);
+template bool optim_pack_op<3>(const OptPackLaunch&);
 }  // namespace dqn

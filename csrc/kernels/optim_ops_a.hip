@@ -4,8 +4,8 @@
 #include "optim_pack.h"
 
 namespace dqn {
-template void optim_pack_op<-1>(const OptPackLaunch&);
-template void optim_pack_op<0>(const OptPackLaunch&);
-template void optim_pack_op<1>(const OptPackLaunch&);
-template void optim_pack_op<2>(const OptPackLaunch&);
+template bool optim_pack_op<-1>(const OptPackLaunch&);
+template bool optim_pack_op<0>(const OptPackLaunch&);
+template bool optim_pack_op<1>(const OptPackLaunch&);
+template bool optim_pack_op<2>(const OptPackLaunch&);
 }  // namespace dqn

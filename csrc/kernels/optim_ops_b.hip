@@ -4,7 +4,7 @@
 #include "optim_pack.h"
 
 namespace dqn {
-template void optim_pack_op<4>(const OptPackLaunch&);
-template void optim_pack_op<5>(const OptPackLaunch&);
-template void optim_pack_op<6>(const OptPackLaunch&);
+template bool optim_pack_op<4>(const OptPackLaunch&);
+template bool optim_pack_op<5>(const OptPackLaunch&);
+template bool optim_pack_op<6>(const OptPackLaunch&);
 }  // namespace dqn

@@ -980,59 +980,50 @@ struct OptPackLaunch {
   const float* part; const WgradGroup* wg; int wg_blocks; DpLaunch dp;
 };
 
+// Launches the kernel of L.mode; false (nothing launched) when that mode is not instantiated.
 template <int N>
-void optim_pack_op(const OptPackLaunch& L);
+bool optim_pack_op(const OptPackLaunch& L);
+
+// THE instantiated modes. The (noisy, target mix, PER) combinations in use -- every one but a target
+// mix without noise -- on top of the bits HI; HI itself is one of: 0, the fused fc weight gradient,
+// + the weight-gradient tiles, + the DP exchange (the fp32 build since round 6 too), and (16-bit
+// builds, the common optimizers) the few-block variant. Each instantiation costs build time and its
+// registers were tuned per mode: a mode missing here is an error, not a silent no-op.
+#define DQN_OPT_MODES_ON(X, HI) \
+  X((HI) | 0) X((HI) | kModeNoisy) X((HI) | kModeNoisy | kModeTmix) X((HI) | kModePer) \
+  X((HI) | kModePer | kModeNoisy) X((HI) | kModePer | kModeNoisy | kModeTmix)
+#define DQN_OPT_MODES(X) \
+  DQN_OPT_MODES_ON(X, 0) DQN_OPT_MODES_ON(X, kModeFc) DQN_OPT_MODES_ON(X, kModeFc | kModeWg) \
+  DQN_OPT_MODES_ON(X, kModeFc | kModeWg | kModeDp)
 
 #ifdef DQN_OPTIM_DEFINE_OPS
 template <int N>
-void optim_pack_op(const OptPackLaunch& L) {
-#define OPM(M) hipLaunchKernelGGL((optim_pack_kernel<N, M>), dim3(L.grid), dim3(kPackThreads), L.dyn, L.st, L.w, L.g, \
+bool optim_pack_op(const OptPackLaunch& L) {
+#define OPM(M) hipLaunchKernelGGL((optim_pack_kernel<N, (M)>), dim3(L.grid), dim3(kPackThreads), L.dyn, L.st, L.w, L.g, \
                                   L.s0, L.s1, L.beta_pow, L.step, L.ticket, L.h, L.jobs, L.njobs, L.packed, L.tgt, \
                                   L.tgt_packed, L.tfreq, L.noise, L.eff, L.gnoise, L.noise_dst, L.noise_n, L.smp, L.per, \
                                   L.tnoise, L.teff, L.tpk, L.noise_rng, L.ff, L.part, L.wg, L.wg_blocks, \
                                   L.dp)
+#define OPM_CASE(M) case (M): OPM(M); return true;
   if constexpr (N < 0) {
     OPM(kModeNoisy);                                    // mix + pack only (noisy nets)
+    return true;
   } else {
-#if DQN_ACT_F32
-    switch (L.mode) {
-      case 0: OPM(0); break; case 1: OPM(1); break; case 3: OPM(3); break;
-      case 4: OPM(4); break; case 5: OPM(5); break; case 7: OPM(7); break;
-      // the fused fc weight gradient / weight-gradient + update / DP exchange modes (round 6: the
-      // fp32 build's FcFuse and fused tiles)
-      case 8: OPM(8); break; case 9: OPM(9); break; case 11: OPM(11); break;
-      case 12: OPM(12); break; case 13: OPM(13); break; case 15: OPM(15); break;
-      case 24: OPM(24); break; case 25: OPM(25); break; case 27: OPM(27); break;
-      case 28: OPM(28); break; case 29: OPM(29); break; case 31: OPM(31); break;
-      case 88: OPM(88); break; case 89: OPM(89); break; case 91: OPM(91); break;
-      case 92: OPM(92); break; case 93: OPM(93); break; case 95: OPM(95); break;
-      default: break;
-    }
-#else
-    constexpr bool kFew = N == 0 || N == 3 || N == 7;   // (the common optimizers' few-block variants)
-    if (kFew && L.few) {
-      if constexpr (kFew) {
-        switch (L.mode) {
-          case 0: OPM(32); break; case 1: OPM(33); break; case 3: OPM(35); break;
-          case 4: OPM(36); break; case 5: OPM(37); break; default: OPM(39); break;
+    constexpr bool kFew = !DQN_ACT_F32 && (N == 0 || N == 3 || N == 7);   // (the common optimizers' few-block variants)
+    if constexpr (kFew) {
+      if (L.few) {
+        switch (L.mode | kModeFew) {
+          DQN_OPT_MODES_ON(OPM_CASE, kModeFew)
+          default: return false;
         }
       }
-    } else {
-      switch (L.mode) {
-        case 0: OPM(0); break; case 1: OPM(1); break; case 3: OPM(3); break;
-        case 4: OPM(4); break; case 5: OPM(5); break; case 7: OPM(7); break;
-        case 8: OPM(8); break; case 9: OPM(9); break; case 11: OPM(11); break;
-        case 12: OPM(12); break; case 13: OPM(13); break; case 15: OPM(15); break;
-        case 24: OPM(24); break; case 25: OPM(25); break; case 27: OPM(27); break;
-        case 28: OPM(28); break; case 29: OPM(29); break; case 31: OPM(31); break;
-        // data parallelism: the WG modes with the in-launch gradient exchange
-        case 88: OPM(88); break; case 89: OPM(89); break; case 91: OPM(91); break;
-        case 92: OPM(92); break; case 93: OPM(93); break; case 95: OPM(95); break;
-        default: break;
-      }
     }
-#endif
+    switch (L.mode) {
+      DQN_OPT_MODES(OPM_CASE)
+      default: return false;
+    }
   }
+#undef OPM_CASE
 #undef OPM
 }
 #endif

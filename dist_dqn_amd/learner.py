@@ -122,7 +122,7 @@ class Learner:
         fuse_wu = int(getattr(config, 'fuse_wgrad_update', 1))
         want_dpx = bool(lr is not None and self._defer_fc and fuse_wu and hasattr(ex, 'can_defer_wgrad')
                         and ex.can_defer_wgrad(B, sg) and config.allreduce in ('xgmi', 'auto'))
-        nslots = sum(1 for it in ex.upd_items if it[20] < 0) if want_dpx else 0
+        nslots = ex.num_dependent_jobs() if want_dpx else 0
         self.reducer = GradAllReducer(self.ctx, network.grad, config.grad_bucket_mb,
                                       'rccl' if ps_client is not None else config.allreduce, config.allreduce_dtype,
                                       gather_bytes=lr['gather_bytes'] if lr else 0, exchange_slots=nslots)
@@ -366,8 +366,7 @@ class Learner:
         optimizer step consumes them)."""
         if self._ps_lowrank is None:
             return None
-        ex = self.net.executor
-        fc, ex._fc_pending = ex._fc_pending, None
+        fc = self.net.executor.take_pending_fc()
         assert fc is not None, 'low-rank push: compute_grads(defer_fc=True) left no fc rows'
         return fc[0], fc[1]
 
@@ -504,8 +503,8 @@ class Learner:
             gk = torch.cuda.CUDAGraph()
             # host-side state a step body advances (restored if the capture is refused midway)
             ex = self.net.executor
-            saved = (self._presampled, getattr(self.net, '_noise_drawn', False), getattr(ex, '_fc_pending', None),
-                     getattr(ex, '_parts_pending', None), getattr(ex, '_wg_pending', None))
+            saved = (self._presampled, getattr(self.net, '_noise_drawn', False),
+                     ex.snapshot_pending() if hasattr(ex, 'snapshot_pending') else None)
             try:
                 with quiet_capture(), torch.cuda.stream(s), \
                         torch.cuda.graph(gk, stream=s, capture_error_mode=_CAPTURE_MODE):
@@ -517,8 +516,8 @@ class Learner:
             except Exception:
                 self._presampled = saved[0]
                 self.net._noise_drawn = saved[1]
-                if hasattr(ex, '_fc_pending'):
-                    ex._fc_pending, ex._parts_pending, ex._wg_pending = saved[2], saved[3], saved[4]
+                if saved[2] is not None:
+                    ex.restore_pending(saved[2])
                 torch.cuda.current_stream(self.device).wait_stream(s)
                 raise
             torch.cuda.current_stream(self.device).wait_stream(s)

@@ -21,6 +21,8 @@ kernels of csrc/kernels/cnn.hip (`HipCnnExecutor`). `simple` uses torch.
 from __future__ import annotations
 
 import os
+from collections import namedtuple
+from types import SimpleNamespace
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -55,6 +57,44 @@ class _Job:
         if self.mode == 3:
             return self.K
         return ((self.K + 31) // 32) * ((self.N + 15) // 16) * 64
+
+
+class _UpdJob:
+    """One row of the fused optimizer's job table: the ints of ``struct UpdJob`` (optim_pack.h), in
+    its field order (``_job_table`` checks the count against the extension's)."""
+    __slots__ = ('kind', 'src_off', 'K', 'N', 'k0', 'n0', 'fwd_off', 'fwd_N16', 'fwd_nt_off', 'fwd_ks_off',
+                 'dg_mode', 'dg_off', 'dg_N16', 'dg_nt_off', 'dg_ks_off', 'dg_cin', 'sig_off', 'ein_off', 'eout_off',
+                 'eff', 'fc_col', 'dep', 'part_off', 'part_n', 'part_stride')
+    _NONE = ('sig_off', 'ein_off', 'eout_off', 'fc_col', 'dep')      # fields whose "absent" is -1, not 0
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k, -1 if k in self._NONE else 0))
+
+    def ints(self):
+        return [getattr(self, k) for k in self.__slots__]
+
+    def replace(self, **kw):
+        return _UpdJob(**{**{k: getattr(self, k) for k in self.__slots__}, **kw})
+
+
+class _Pending:
+    """What a ``loss_and_grad`` leaves for the next optimizer launch to finish. ``fc``: (x ptr, dh
+    ptr, rows) of a step whose fc weight gradient the launch forms (defer_fc); ``wg``: (members,
+    dims, scales) of the grouped conv / output-layer weight gradients it computes in its first
+    blocks (defer_wgrad); ``parts``: (job table, partial buffer ptr) of the deterministic conv
+    partials it sums (det_wgrad)."""
+    __slots__ = ('fc', 'wg', 'parts')
+
+    def __init__(self, fc=None, wg=None, parts=None):
+        self.fc, self.wg, self.parts = fc, wg, parts
+
+
+# what one ``loss_and_grad`` does (``HipExecutor._resolve``). gnoise: noise of the dL/dsigma split (or
+# None), noisy: that split runs, defer: fc gradient left to the optimizer launch, dwg: the grouped
+# weight gradients too, det: deterministic conv partials, chain: fc / conv3 / conv2 dgrads in one
+# launch, zero_in_head: the fc dgrad launch zeroes the conv gradient range (else a memset does)
+_StepFlags = namedtuple('_StepFlags', 'split gnoise noisy defer dwg det chain zero_in_head')
 
 
 def _frag_elems(K, N):
@@ -127,7 +167,6 @@ class HipExecutor:
         # 4.96 + 5.16 us for the two launches (the waits and the write-through stores cost more than the
         # launch boundary saves; 14.34k / 13.99k / 14.50k steps/s for 1 / 2 / 0, profiles/r4_dgrad_chain_ab.jsonl)
         self.chain_dgrad = 0
-        self._fc_zero = None        # int32 counters the next fc forward launch zeroes (the chain's)
         self.grouped_wgrad = True   # every layer's weight gradient in ONE launch after the dgrad chain
         # (round 2 measured the fc + output-layer members on a parallel graph branch beside the dgrad
         # chain: 12.0k -> 9.9k steps/s, the captured fork / join costs more than the overlap gains)
@@ -262,12 +301,13 @@ class HipExecutor:
             eff = int(self.noisy and src not in fc_w) | (2 if self.tfact and src in fc_w else 0)
             fcc = fc_col.get(src, -1)
             assert fcc < 0 or (f.K % 8 == 0 and f.N % 8 == 0)
+            dgf = dict(dg_mode=d.mode, dg_off=d.dst_off, dg_N16=d.dst_N16, dg_nt_off=d.nt_off, dg_ks_off=d.ks_off,
+                       dg_cin=d.p1) if d else {}
             for k0 in range(0, f.K, 32):
                 for n0 in range(0, f.N, 64):
-                    items.append([0, src, f.K, f.N, k0, n0, f.dst_off, f.dst_N16, f.nt_off, f.ks_off,
-                                  d.mode if d else 0, d.dst_off if d else 0, d.dst_N16 if d else 0,
-                                  d.nt_off if d else 0, d.ks_off if d else 0, d.p1 if d else 0, so, ei, eo, eff,
-                                  fcc, -1, 0, 0, 0])
+                    items.append(_UpdJob(kind=0, src_off=src, K=f.K, N=f.N, k0=k0, n0=n0, fwd_off=f.dst_off,
+                                         fwd_N16=f.dst_N16, fwd_nt_off=f.nt_off, fwd_ks_off=f.ks_off, sig_off=so,
+                                         ein_off=ei, eout_off=eo, eff=eff, fc_col=fcc, **dgf))
         for name in lay.names:
             off, n = lay.offsets[name], lay.numel(name)
             if off in fwd or off in sig:
@@ -278,16 +318,12 @@ class HipExecutor:
             assert fcc < 0 or n <= 512, 'fused fc bias gradient: one chunk of <= 512 values'
             for s0 in range(0, n, 2048):
                 cnt = min(2048, n - s0)
-                items.append([1, off + s0, cnt, 0, 0, 0, (c.dst_off + self.fs * s0) if c else -1] + [0] * 9
-                             + [so + s0 if so >= 0 else -1, -1, eo + s0 if so >= 0 else -1, int(self.noisy), fcc,
-                                -1, 0, 0, 0])
+                items.append(_UpdJob(kind=1, src_off=off + s0, K=cnt, fwd_off=(c.dst_off + self.fs * s0) if c else -1,
+                                     sig_off=so + s0 if so >= 0 else -1, eout_off=eo + s0 if so >= 0 else -1,
+                                     eff=int(self.noisy), fc_col=fcc))
         self.upd_items = items
         self._upd_dev: Dict[torch.device, torch.Tensor] = {}
-        # (x ptr, dh ptr, rows) of a step whose fc weight gradient the next update_and_pack forms
-        self._fc_pending = None
-        # (members, dims, scales) of a step whose grouped conv / output-layer weight gradients the
-        # next update_and_pack computes in its first launch (loss_and_grad(defer_wgrad=True))
-        self._wg_pending = None
+        self._pending = _Pending()
         self._wg_plans: Dict[tuple, tuple] = {}
         # 128-row chunks per conv weight-gradient tile of the fused launch (KernelTuning.wg_conv_chunks)
         self.wg_conv_chunks = self.tuning.conv_chunks(self.arch.network, self.compute_dtype)
@@ -295,21 +331,41 @@ class HipExecutor:
         # uses to sum the dependent jobs' gradients over every rank (parallel/xgmi.py dpx_launch); None:
         # one process
         self.dp_exchange = None
-        # (job table, partial buffer ptr) of a step whose conv weight gradients the next
-        # update_and_pack sums from the grouped wgrad's deterministic partials
-        self._parts_pending = None
         self._det: Dict[tuple, dict] = {}
         self._bound: Dict[int, torch.Tensor] = {}   # flat ptr -> noise its packed/eff buffers reflect
         self._dummies: Dict[torch.device, tuple] = {}
 
+    def _job_table(self, items, dev) -> torch.Tensor:
+        assert len(_UpdJob.__slots__) == self.ext.UPD_JOB_INTS, 'UpdJob: field list out of step with optim_pack.h'
+        return torch.tensor([v for it in items for v in it.ints()], dtype=torch.int32, device=dev)
+
     def _upd_jobs(self, dev):
         jobs = self._upd_dev.get(dev)
         if jobs is None:
-            ints = [v for it in self.upd_items for v in it]
-            assert len(ints) == len(self.upd_items) * self.ext.UPD_JOB_INTS
-            jobs = torch.tensor(ints, dtype=torch.int32, device=dev)
-            self._upd_dev[dev] = jobs
+            jobs = self._upd_dev[dev] = self._job_table(self.upd_items, dev)
         return jobs
+
+    def num_dependent_jobs(self) -> int:
+        """Update jobs whose gradient another launch (or this one's weight-gradient tiles) produces:
+        all but the fc jobs, which form theirs from the FcFuse rows."""
+        return sum(1 for it in self.upd_items if it.fc_col < 0)
+
+    # -------------------------------------------------- hand-off to the optimizer launch
+    def pending_fc(self) -> bool:
+        p = self._pending
+        return p.fc is not None or p.parts is not None or p.wg is not None
+
+    def snapshot_pending(self) -> _Pending:
+        p = self._pending
+        return _Pending(p.fc, p.wg, p.parts)
+
+    def restore_pending(self, saved: _Pending):
+        self._pending = _Pending(saved.fc, saved.wg, saved.parts)
+
+    def take_pending_fc(self):
+        """The deferred fc gradient's (x ptr, dh ptr, rows), or None; no optimizer launch consumes it then."""
+        fc, self._pending.fc = self._pending.fc, None
+        return fc
 
     def _eff_for(self, key: int, like: torch.Tensor) -> torch.Tensor:
         eff = self._eff.get(key)
@@ -389,20 +445,48 @@ class HipExecutor:
         (default: taken from this executor; the launch forms dW = X^T dH and the fc bias gradient
         from those rows instead of reading them from ``grad``). ``pack=False``: the update only, no packed
         fragments written (a caller that never runs the network until it repacks). Returns True."""
-        from ..optim import kernel_op
         dev = flat.device
-        assert pack or (self._wg_pending is None and not self.noisy), 'pack=False: plain fused update only'
-        if self._wg_pending is not None:
-            return self._update_split(opt, flat, grad, grad_scale, global_step, target, target_freq, noise, grad_noise,
-                                      noise_dst, next_sample, target_noise, noise_rng, fc)
+        pend = self._pending
+        assert pack or (pend.wg is None and not self.noisy), 'pack=False: plain fused update only'
+        fcargs = self._fc_args(fc if fc is not None else self.take_pending_fc())
+        if pend.wg is not None:
+            # ``update_and_pack`` after ``loss_and_grad(defer_wgrad=True)``: ONE launch that also
+            # computes the grouped weight gradients (conv layers + output layer, fp32 atomics into
+            # ``grad``, optim_pack.h kModeWg). Its grid: the lead block (next minibatch + end-of-launch
+            # bookkeeping), the weight-gradient tiles, the fc jobs (gradient formed from the FcFuse
+            # rows: independent of the tiles -- the fc update, ~90% of the optimizer's bytes, runs
+            # beside the weight-gradient work). Every other job has a block at the end of the grid that
+            # waits for the tiles of its gradient's K-range.
+            wg, pend.wg = pend.wg, None
+            assert fcargs, 'deferred weight gradients need the fused fc gradient (defer_fc)'
+            plan, nwg, jobs, _, _, lead, ndep = self._wg_plan(wg, grad, dev)
+            # data parallelism: the dependent jobs sum their gradient over every rank inside the launch
+            dp = self.dp_exchange.dpx_launch(lead, ndep) if self.dp_exchange is not None else []
+            return self._launch_update(opt, flat, grad, grad_scale, global_step, target, target_freq, noise, grad_noise,
+                                       noise_dst, next_sample, target_noise, noise_rng, fcargs, jobs, 0,
+                                       wg=plan.data_ptr(), wg_blocks=nwg, dp=dp)
         jobs, part = self._upd_jobs(dev), 0
-        if self._parts_pending is not None:
-            (jobs, part), self._parts_pending = self._parts_pending, None
+        if pend.parts is not None:
+            (jobs, part), pend.parts = pend.parts, None
+        return self._launch_update(opt, flat, grad, grad_scale, global_step, target, target_freq, noise, grad_noise,
+                                   noise_dst, next_sample, target_noise, noise_rng, fcargs, jobs, part,
+                                   no_pack=not pack)
+
+    def _opt_ticket(self, opt, dev) -> torch.Tensor:
+        if getattr(opt, 'ticket', None) is None or opt.ticket.device != dev or opt.ticket.numel() < 17 * 32:
+            opt.ticket = torch.zeros(17 * 32, dtype=torch.int32, device=dev)   # 1 + 16 sub-tickets, 128 B apart
+        return opt.ticket
+
+    def _launch_update(self, opt, flat, grad, grad_scale, global_step, target, target_freq, noise, grad_noise,
+                       noise_dst, next_sample, target_noise, noise_rng, fcargs, jobs, part, **launch_kw):
+        """THE optimizer launch: the argument block every variant shares (ticket, slots,
+        hyper-parameters, noisy eff / packed / target buffers, sampler lists) around the caller's job
+        table, partial buffer and ``launch_kw`` (wg / wg_blocks / dp, or no_pack)."""
+        from ..optim import kernel_op
         hp = opt.hp
         s0 = opt.slots[0] if len(opt.slots) > 0 else flat
         s1 = opt.slots[1] if len(opt.slots) > 1 else flat
-        if getattr(opt, 'ticket', None) is None or opt.ticket.device != dev or opt.ticket.numel() < 17 * 32:
-            opt.ticket = torch.zeros(17 * 32, dtype=torch.int32, device=dev)   # 1 + 16 sub-tickets, 128 B apart
+        ticket = self._opt_ticket(opt, flat.device)
         eff = teff = tpk = None
         if self.noisy:
             assert noise is not None and noise.dtype == torch.float32
@@ -416,18 +500,18 @@ class HipExecutor:
         else:
             p = self.packed(flat)
             pt = self.packed(target) if target is not None else None
-        self.ext.optim_pack(kernel_op(opt), flat, grad, s0, s1, opt.beta_powers, opt.ticket, float(opt.lr),
+        kind = next_sample['kind'] if next_sample is not None else None
+        self.ext.optim_pack(kernel_op(opt), flat, grad, s0, s1, opt.beta_powers, ticket, float(opt.lr),
                             float(opt.reg_param), int(opt.layout.reg_end), float(grad_scale), global_step,
                             [float(hp['momentum']), float(hp['rho']), float(hp['rms_mom']), float(hp['rms_eps']),
                              float(hp['b1']), float(hp['b2']), float(hp['adam_eps']), float(hp['ad_rho']),
                              float(hp['ad_eps'])], jobs, p, target, pt, int(target_freq), self.opt_max_grid,
                             noise, eff, grad_noise, noise_dst,
-                            (list(next_sample['spec']) + [int(next_sample['B'])]
-                             if next_sample is not None and next_sample['kind'] == 'uniform' else []),
-                            (list(next_sample['p']) if next_sample is not None and next_sample['kind'] == 'per' else []),
-                            (list(next_sample['f']) if next_sample is not None and next_sample['kind'] == 'per' else []),
-                            target_noise, teff, tpk, noise_rng, self._take_fc(fc), part, tsg=self._tsg_arg(target, target_noise),
-                            no_pack=not pack)
+                            list(next_sample['spec']) + [int(next_sample['B'])] if kind == 'uniform' else [],
+                            list(next_sample['p']) if kind == 'per' else [],
+                            list(next_sample['f']) if kind == 'per' else [],
+                            target_noise, teff, tpk, noise_rng, fcargs, part, tsg=self._tsg_arg(target, target_noise),
+                            **launch_kw)
         if self.noisy:
             self._bound[flat.data_ptr()] = noise_dst if noise_dst is not None else noise
             if target_noise is not None:
@@ -438,10 +522,8 @@ class HipExecutor:
         """Allocate what ``update_and_pack`` creates on first use (the device job table, the
         optimizer's arrival ticket, the packed buffer), so a first call inside a graph capture does
         no host-to-device copy."""
-        dev = flat.device
-        self._upd_jobs(dev)
-        if getattr(opt, 'ticket', None) is None or opt.ticket.device != dev or opt.ticket.numel() < 17 * 32:
-            opt.ticket = torch.zeros(17 * 32, dtype=torch.int32, device=dev)
+        self._upd_jobs(flat.device)
+        self._opt_ticket(opt, flat.device)
         self.packed(flat)
 
     def _tsg_arg(self, target, target_noise) -> int:
@@ -484,19 +566,18 @@ class HipExecutor:
                         span[o] = (mi, o + lay.numel(name), j % 2 == 0)
             fcj, groups = [], {}
             for it in self.upd_items:
-                if it[20] >= 0:
-                    fcj.append(list(it))
+                if it.fc_col >= 0:
+                    fcj.append(it)
                     continue
-                src = it[1]
-                owner = [(mi, w) for o, (mi, hi, w) in span.items() if o <= src < hi]
-                assert len(owner) == 1, 'fused wgrad: no member writes the gradient of job at %d' % src
+                owner = [(mi, w) for o, (mi, hi, w) in span.items() if o <= it.src_off < hi]
+                assert len(owner) == 1, 'fused wgrad: no member writes the gradient of job at %d' % it.src_off
                 mi, w = owner[0]
                 if w:
-                    assert it[0] == 0, 'weight gradients of fused members come as tile jobs'
-                    slot = it[4] // 64                  # the tile's K-range (64 rows per fused tile)
+                    assert it.kind == 0, 'weight gradients of fused members come as tile jobs'
+                    slot = it.k0 // 64                  # the tile's K-range (64 rows per fused tile)
                 else:
                     slot = ext.WG_SLOTS - 1
-                groups.setdefault((mi, slot), []).append(list(it))
+                groups.setdefault((mi, slot), []).append(it)
             # range-dependent jobs right after the tiles (their waits end when the tiles do) or at the
             # end of the grid: first measured +1.2% for noisy nets, whose fc jobs run ~10 us each and
             # kept them queued to ~45 us; -0.2..-1.0% for the plain nets (profiles/r4_dep_first_ab.txt).
@@ -508,84 +589,28 @@ class HipExecutor:
             table, deps = list(fcj[:lead]), []
             for (mi, slot), its in sorted(groups.items()):
                 deps.append([mi, slot, len(table), len(its)])
-                for it in its:                 # the job's block waits for that range's tiles
-                    it[21] = mi * ext.WG_SLOTS + slot
-                table += its
+                # (the job's block waits for that range's tiles)
+                table += [it.replace(dep=mi * ext.WG_SLOTS + slot) for it in its]
             table += fcj[lead:]
             host, total = ext.qnet_wgrad_plan(members, dims, scales, done, deps, conv_chunks=self.wg_conv_chunks)
-            jobs = torch.tensor([v for it in table for v in it], dtype=torch.int32, device=dev)
+            jobs = self._job_table(table, dev)
             # (the dependent jobs: table positions [lead, lead + ndep))
             pl = (host.to(dev), int(total), jobs, len(fcj), done, lead, len(table) - len(fcj))
             self._wg_plans[key] = pl
         return pl
 
-    def _update_split(self, opt, flat, grad, grad_scale, global_step, target, target_freq, noise, grad_noise,
-                      noise_dst, next_sample, target_noise, noise_rng, fc):
-        """``update_and_pack`` after ``loss_and_grad(defer_wgrad=True)``: ONE launch that also
-        computes the grouped weight gradients (conv layers + output layer, fp32 atomics into
-        ``grad``, optim_pack.h kModeWg). Its grid: the lead block (next minibatch + end-of-launch
-        bookkeeping), the weight-gradient tiles, the fc jobs (gradient formed from the FcFuse
-        rows: independent of the tiles -- the fc update, ~90% of the optimizer's bytes, runs
-        beside the weight-gradient work). Every other job has a block at the end of the grid that
-        waits for the tiles of its gradient's K-range."""
-        from ..optim import kernel_op
-        dev = flat.device
-        wg, self._wg_pending = self._wg_pending, None
-        fcargs = self._take_fc(fc)
-        assert fcargs, 'deferred weight gradients need the fused fc gradient (defer_fc)'
-        plan, nwg, jobs, nfc, _, lead, ndep = self._wg_plan(wg, grad, dev)
-        # data parallelism: the dependent jobs sum their gradient over every rank inside the launch
-        dp = self.dp_exchange.dpx_launch(lead, ndep) if self.dp_exchange is not None else []
-        hp = opt.hp
-        s0 = opt.slots[0] if len(opt.slots) > 0 else flat
-        s1 = opt.slots[1] if len(opt.slots) > 1 else flat
-        if getattr(opt, 'ticket', None) is None or opt.ticket.device != dev or opt.ticket.numel() < 17 * 32:
-            opt.ticket = torch.zeros(17 * 32, dtype=torch.int32, device=dev)
-        eff = teff = tpk = None
-        if self.noisy:
-            assert noise is not None and noise.dtype == torch.float32
-            k = flat.data_ptr()
-            p, eff = self._packed_for(k, flat), self._eff_for(k, flat)
-            pt = None
-            if target_noise is not None:
-                assert target is not None and target_noise.dtype == torch.float32
-                tk = target.data_ptr()
-                tpk, teff = self._packed_for(tk, target), self._eff_for(tk, target)
-        else:
-            p = self.packed(flat)
-            pt = self.packed(target) if target is not None else None
-        hps = [float(hp['momentum']), float(hp['rho']), float(hp['rms_mom']), float(hp['rms_eps']), float(hp['b1']),
-               float(hp['b2']), float(hp['adam_eps']), float(hp['ad_rho']), float(hp['ad_eps'])]
-        op = kernel_op(opt)
-        args = (flat, grad, s0, s1, opt.beta_powers, opt.ticket, float(opt.lr), float(opt.reg_param),
-                int(opt.layout.reg_end), float(grad_scale), global_step, hps)
-        self.ext.optim_pack(op, *args, jobs, p, target, pt, int(target_freq), self.opt_max_grid, noise, eff,
-                            grad_noise, noise_dst,
-                            (list(next_sample['spec']) + [int(next_sample['B'])]
-                             if next_sample is not None and next_sample['kind'] == 'uniform' else []),
-                            (list(next_sample['p']) if next_sample is not None and next_sample['kind'] == 'per' else []),
-                            (list(next_sample['f']) if next_sample is not None and next_sample['kind'] == 'per' else []),
-                            target_noise, teff, tpk, noise_rng, fcargs, 0, wg=plan.data_ptr(), wg_blocks=nwg,
-                            dp=dp, tsg=self._tsg_arg(target, target_noise))
-        if self.noisy:
-            self._bound[flat.data_ptr()] = noise_dst if noise_dst is not None else noise
-            if target_noise is not None:
-                self._bound[target.data_ptr()] = target_noise
-        return True
-
     def can_defer_wgrad(self, B: int, sigma_grads: bool = False) -> bool:
         """True when ``loss_and_grad(defer_fc=True, defer_wgrad=True)`` at this batch leaves the
         grouped conv / output-layer weight gradients to the next ``update_and_pack`` (which then
-        runs them beside the fc update, ``_update_split``): the Nature trunk's grouped-wgrad path
+        runs them beside the fc update): the Nature trunk's grouped-wgrad path
         in the 16-bit builds. Under data parallelism only with ``dp_exchange`` set (the launch sums
         those gradients over the ranks itself) and the low-rank fc exchange."""
         # (the reference `cnn` too: its conv members are the same three fused tile kinds -- 8x8/4, 4x4/2,
         #  3x3/1 -- with SAME padding in their ConvArgs, conv2 / conv3 reading the pooled activations)
         return self.can_defer_fc(B, sigma_grads) and not (self.noisy and sigma_grads)
 
-    def _take_fc(self, fc=None):
-        if fc is None:
-            fc, self._fc_pending = self._fc_pending, None
+    def _fc_args(self, fc) -> list:
+        """The optimizer launch's FcFuse argument of pending fc rows (x ptr, dh ptr, rows); [] for None."""
         if fc is None:
             return []
         x, dh, M = fc
@@ -596,9 +621,6 @@ class HipExecutor:
         gradient to the fused optimizer launch (16-bit builds, grouped-wgrad path)."""
         return (bool(getattr(self.ext, 'OPTIM_FC_FUSE', 0)) and self.grouped_wgrad and not self.two_stream
                 and B <= 32 and not (self.noisy and sigma_grads))
-
-    def pending_fc(self) -> bool:
-        return self._fc_pending is not None or self._parts_pending is not None or self._wg_pending is not None
 
     def can_det_wgrad(self, B: int) -> bool:
         """True when ``loss_and_grad(det_wgrad=True)`` leaves the conv weight / bias gradients as
@@ -638,17 +660,13 @@ class HipExecutor:
             by_off[lay.offsets[name + '/b']] = (b0 + K * N, ng, stride)
         first, rest = [], []
         for it in self.upd_items:
-            it = list(it)
             # tile jobs: src_off is the tensor's; chunk jobs: the chunk's (bias chunks start at 0)
-            hit = by_off.get(it[1])
-            if hit is not None:
-                it[-3:] = list(hit)
-                first.append(it)     # the long-latency summing jobs first in the launch
+            part = by_off.get(it.src_off)
+            if part is not None:     # the long-latency summing jobs first in the launch
+                first.append(it.replace(part_off=part[0], part_n=part[1], part_stride=part[2]))
             else:
                 rest.append(it)
-        ints = [v for it in first + rest for v in it]
-        pl = {'buf': buf, 'info': info,
-              'jobs': torch.tensor(ints, dtype=torch.int32, device=dev)}
+        pl = {'buf': buf, 'info': info, 'jobs': self._job_table(first + rest, dev)}
         self._det[key] = pl
         return pl
 
@@ -738,11 +756,9 @@ class HipExecutor:
         return t
 
     def packed(self, flat: torch.Tensor) -> torch.Tensor:
-        key = flat.data_ptr()
-        p = self._packed.get(key)
-        if p is None:
-            p = torch.zeros(self.packed_elems, dtype=self.act_dtype, device=flat.device)
-            self._packed[key] = p
+        fresh = flat.data_ptr() not in self._packed
+        p = self._packed_for(flat.data_ptr(), flat)
+        if fresh:
             self.repack(flat)
         return p
 
@@ -817,13 +833,11 @@ class HipExecutor:
 
     def _lowrank_ws(self, B: int, W: int, dev) -> dict:
         key = (B, W, dev)
-        lw = getattr(self, '_lr_bufs', {}).get(key)
+        lw = self._ws.get(('lowrank',) + key)
         if lw is None:
-            if not hasattr(self, '_lr_bufs'):
-                self._lr_bufs = {}
             lw = {'x': torch.zeros(W * B * self.FLAT, dtype=self.act_dtype, device=dev),
                   'dh': torch.zeros(W * B * self.HH, dtype=self.act_dtype, device=dev)}
-            self._lr_bufs[key] = lw
+            self._ws[('lowrank',) + key] = lw
         return lw
 
     def _side_stream(self, dev):
@@ -890,11 +904,13 @@ class HipExecutor:
         """The fused trunk can draw the uniform minibatch itself (replay.sample_slots(defer))."""
         return self.fused_trunk
 
-    def _fwd_trunk(self, xs, packs, flats, ws, B, ninst, frames=None, keep_acts=True, M=(), sample=None, fc=True):
+    def _fwd_trunk(self, xs, packs, flats, ws, B, ninst, frames=None, keep_acts=True, M=(), sample=None, fc=True,
+                   fc_zero=None):
         """conv1..fc for `ninst` instances -> ws['h'] (M: valid rows per instance, e.g. the
         fused actor instance's E < B). sample: (spec pointers, sampled instances) — the
         trunk draws the uniform batch itself (the slot tables of those instances are outputs).
-        fc=False: stop at conv3 (the caller's fused fc + head launch follows, ``_fc_head``).
+        fc=False: stop at conv3 (the caller's fused fc + head launch follows, ``_fc_head``). fc_zero: see
+        ``_fc_fwd``.
 
         xs: uint8 NHWC [B, 84, 84, 4] inputs, or (frames given) int32 [B, 4] slot
         tables into the frame ring ``frames`` [F, 84, 84] (fused gather)."""
@@ -919,7 +935,7 @@ class HipExecutor:
             ext.qnet_trunk(frames.data_ptr() if frames is not None else 0, ptrs, B, ninst, self.input_scale, prof,
                            list(M), smp)
             if fc:
-                self._fc_fwd(packs, flats, ws, B, ninst)
+                self._fc_fwd(packs, flats, ws, B, ninst, fc_zero)
             return
         d1 = [B * h1 * w1, c1.cout, c1.k * c1.k * c1.cin, (c1.cout + 15) // 16, c1.cout, 84, 84, h1, w1, 0, 0]
         kind1 = _KIND['C1']
@@ -935,11 +951,11 @@ class HipExecutor:
                        [rows(ws['x3'], i) for i in range(ninst)], [], [1.0] * ninst,
                        [B * h3 * w3, c3.cout, c3.k * c3.k * c3.cin, c3.cout // 16, c3.cout, h2, w2, h3, w3, 0, 0])
         if fc:
-            self._fc_fwd(packs, flats, ws, B, ninst)
+            self._fc_fwd(packs, flats, ws, B, ninst, fc_zero)
 
-    def _fc_fwd(self, packs, flats, ws, B, ninst):
+    def _fc_fwd(self, packs, flats, ws, B, ninst, z=None):
+        """z: int32 counters this launch zeroes (the step's dgrad-chain counters)."""
         fcb = [p.data_ptr() + self.esz * self.poff['fc/bias'] for p in packs]
-        z = self._fc_zero                  # (the step's dgrad-chain counters: zeroed by this launch)
         self.ext.qnet_igemm(_KIND['DFWD'], [ws['x3'][i].data_ptr() for i in range(ninst)],
                             [p.data_ptr() + self.esz * self.poff['fc/fwd'] for p in packs], fcb,
                             [ws['h'][i].data_ptr() for i in range(ninst)], [], [1.0] * ninst,
@@ -994,7 +1010,7 @@ class HipExecutor:
                     out.append(v)
         return out
 
-    def _fc_head(self, packs, ws, B, nlearn, ints, w, b, wv, bv, io, actor, actor_f, act_h, dev):
+    def _fc_head(self, packs, ws, B, nlearn, ints, w, b, wv, bv, io, actor, actor_f, act_h, dev, fc_zero=None):
         """fc forward of every instance (learners', then the fused actors') + the scalar head's
         loss / dQ / dH (+ the fused acting step) in ONE launch (``can_fold_head``)."""
         n = len(packs)
@@ -1008,7 +1024,7 @@ class HipExecutor:
                               [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()], actor, actor_f, act_h,
                               [fw['q'].data_ptr(), fw['cnt'].data_ptr(), fw['mpad'], nlearn,
                                fw['dqg'].data_ptr() if self.fold_spin else 0, fw['epoch'].data_ptr()] +
-                              ([self._fc_zero.data_ptr(), self._fc_zero.numel()] if self._fc_zero is not None else []),
+                              ([fc_zero.data_ptr(), fc_zero.numel()] if fc_zero is not None else []),
                               self.fold_prof.data_ptr() if self.fold_prof is not None else 0,
                               two_per_cu=bool(self.tuning.fold_two_per_cu))
 
@@ -1033,37 +1049,37 @@ class HipExecutor:
     def forward(self, flat, x, noise=None):
         return self.q_values(flat, x, noise)
 
-    def _c51_logits(self, hs, pwc, pbias):
+    def _c51_logits(self, hs, pwc, pbias, B, dev):
         """C51 logits of every instance as fp32 rows [B][KD] (logits | pad | dueling value logits
         at VO) from ONE igemm launch over the combined output layer (``head/wc``): spread over
         many CUs instead of re-streaming the output layer through one CU per head workgroup."""
-        B, KD = self._c51_B, self.c51_KD
+        KD = self.c51_KD
         n = len(hs)
-        ws = self._c51_ws(B)
+        ws = self._c51_ws(B, dev)
         lg = [ws['lg'][i].data_ptr() for i in range(n)]
         self.ext.qnet_igemm(_KIND['DF32'], list(hs), pwc, pbias, lg, [], [1.0] * n,
                             [B, KD, self.HH, KD // 16, KD, 0, self.HH, 0, 0, 0, 0])
         return lg
 
-    def _c51_ws(self, B):
+    def _c51_ws(self, B, dev):
         key = ('c51', B)
         ws = self._ws.get(key)
         if ws is None:
-            ws = {'lg': torch.zeros(4, B * self.c51_KD, dtype=torch.float32, device=self._c51_dev)}
+            ws = {'lg': torch.zeros(4, B * self.c51_KD, dtype=torch.float32, device=dev)}
             self._ws[key] = ws
         return ws
 
     def _head(self, ints, hs, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h=0, ws=None):
         """Output layer + loss (+ backward) launch: scalar head or the C51 head."""
         if self.dist:
-            self._c51_B = ints[0]
+            B, dev = ints[0], ws['dq16'].device
             # (pw, pwv = the combined output layer's fragments and bias rows, see _head_packs)
             if act_h:
                 # fused acting: the actors' logits ride in the same igemm launch as one more
                 # instance (online weights), the acting step in more C51-head workgroups
-                lg = self._c51_logits(list(hs) + [act_h], list(pw) + [pw[0]], list(pwv) + [pwv[0]])
+                lg = self._c51_logits(list(hs) + [act_h], list(pw) + [pw[0]], list(pwv) + [pwv[0]], B, dev)
             else:
-                lg = self._c51_logits(hs, pw, pwv)
+                lg = self._c51_logits(hs, pw, pwv, B, dev)
             qp = [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()] if not ints[5] else []
             prof = self.head_prof.data_ptr() if self.head_prof is not None and not ints[5] else 0
             self.ext.qnet_c51_head(ints, [self.atoms], [float(self.arch.v_min), float(self.arch.v_max)], hs, w, b,
@@ -1085,7 +1101,6 @@ class HipExecutor:
         w, b, wv, bv = self._head_ptrs([fl])
         q = torch.empty(B, self.A, dtype=torch.float32, device=x.device)
         pw, pwv = self._head_packs([p])
-        self._c51_dev = x.device
         self._head([B, self.A, self.HID, int(self.dueling), 0, 1], [ws['h'][0].data_ptr()],
                    w, b, wv, bv, [0] * 7 + [q.data_ptr()] + [0] * 5, pw, pwv, [], [], [], ws=ws)
         return q
@@ -1103,7 +1118,6 @@ class HipExecutor:
         self._fwd_trunk([stacks], [p], [fl], ws, E, 1, frames=frames, keep_acts=False)
         w, b, wv, bv = self._head_ptrs([fl])
         pw, pwv = self._head_packs([p])
-        self._c51_dev = frames.device
         self._head([E, self.A, self.HID, int(self.dueling), 0, 1], [ws['h'][0].data_ptr()],
                    w, b, wv, bv, [0] * 7 + [q_out.data_ptr() if q_out is not None else 0] + [0] * 5,
                    pw, pwv, [], list(actor_ptrs) + list(actor_ints), list(actor_f), ws=ws)
@@ -1172,7 +1186,7 @@ class HipExecutor:
         return t
 
     def _head_wgrad_members(self, ws, B, h0, hgrads):
-        """Grouped-wgrad members of the output layer: dW = h^T dZ (dueling: advantage stream over
+        """Grouped-wgrad (member, dims) pairs of the output layer: dW = h^T dZ (dueling: advantage stream over
         h's second half, value stream over its first half) from the head's dZ rows (dq16):
         scalar heads dQ (ld 64, value dQ in column 32), C51 dL/dlogits (ld KD, value at VO)."""
         dw, db, dwv, dbv = hgrads
@@ -1181,11 +1195,12 @@ class HipExecutor:
         ld, vo = (self.c51_KD, self.c51_VO) if self.dist else (64, 32)
         dq = ws['dq16'].data_ptr()
         esz = ws['dq16'].element_size()
-        if not self.dueling:
-            return ([[_KIND['HW'], h0, dq, ld, dw, db, 0, 0, N, N]], [[B, N, H, 0, 0, 0, HH, 0, 0, 0, 0]])
-        return ([[_KIND['HW'], h0 + esz * H, dq, ld, dw, db, 0, 0, N, N],
-                 [_KIND['HW'], h0, dq + esz * vo, ld, dwv, dbv, 0, 0, NV, NV]],
-                [[B, N, H, 0, 0, 0, HH, 0, 0, 0, 0], [B, NV, H, 0, 0, 0, HH, 0, 0, 0, 0]])
+        adv = [_KIND['HW'], h0 + (esz * H if self.dueling else 0), dq, ld, dw, db, 0, 0, N, N]
+        pairs = [(adv, [B, N, H, 0, 0, 0, HH, 0, 0, 0, 0])]
+        if self.dueling:
+            pairs.append(([_KIND['HW'], h0, dq + esz * vo, ld, dwv, dbv, 0, 0, NV, NV],
+                          [B, NV, H, 0, 0, 0, HH, 0, 0, 0, 0]))
+        return pairs
 
     # ----------------------------------------------------------- training
     def supports_fused_acting(self) -> bool:
@@ -1208,7 +1223,7 @@ class HipExecutor:
         defer_wgrad (``can_defer_wgrad``, with defer_fc, one process): the grouped conv and
         output-layer weight / bias gradients are NOT launched here either; the next
         ``update_and_pack`` computes them in the leading blocks of its first launch, beside the fc
-        update (``_update_split``). ``grad_out`` holds them only after that call.
+        update. ``grad_out`` holds them only after that call.
 
         det_wgrad (``can_det_wgrad``, one process): the conv weight / bias gradients are NOT
         written to grad_out either; the grouped wgrad launch stores per-chunk-group partials
@@ -1234,8 +1249,39 @@ class HipExecutor:
         ~95% of Nature-CNN's bytes, is final when it returns) and ``tail()`` launches the conv
         backward. The learner starts the all-reduce of the dense range between the two, so it
         overlaps the conv backward. ``tail`` is None when this network has no split point."""
-        ext, lay = self.ext, self.layout
-        gnoise = noise if sigma_grads else None      # noise of the dL/dsigma split (None: skip it)
+        st = self._begin_step(online, target, batch, grad_out, noise, noise_target, acting)
+        fl = self._resolve(st.B, split, noise if sigma_grads else None, lowrank, defer_fc, det_wgrad, defer_wgrad)
+        self._forward(st, fl)
+        self._head_loss(st, fl, batch)
+        tail = self._backward(st, fl, draw_noise, lowrank)
+        return (st.ws['loss'], st.ws['prio'], tail) if split else (st.ws['loss'], st.ws['prio'])
+
+    _defer_wgrad_needs = 'defer_wgrad: needs defer_fc, no det_wgrad; under DP the low-rank exchange and dp_exchange'
+
+    def _resolve(self, B, split, gnoise, lowrank, defer_fc, det_wgrad, defer_wgrad) -> _StepFlags:
+        """The caller's flags and this executor's state -> what the step does, with every
+        availability check. gnoise: the noise of the dL/dsigma split (None: skip it)."""
+        sg = gnoise is not None
+        det = bool(det_wgrad)
+        assert not det or (self.can_det_wgrad(B) and lowrank is None), 'det_wgrad: not available here'
+        defer = bool(defer_fc) and self.can_defer_fc(B, sg)
+        assert defer or not defer_fc, 'defer_fc: not available for this executor / batch'
+        dwg = bool(defer_wgrad)
+        # (under DP the deferred gradients need the low-rank fc rows of every rank: ``lowrank_spec`` is
+        #  None for the cnn, whose backward ignores ``lowrank`` -- it defers in one process only)
+        dp_ok = not split or (lowrank is not None and self.dp_exchange is not None
+                              and self.lowrank_spec(B, sigma_fused=True) is not None)
+        assert not dwg or (defer and not det and self.can_defer_wgrad(B, sg) and dp_ok), self._defer_wgrad_needs
+        # the fc / conv3 / conv2 dgrads as one launch (single-process grouped-wgrad path)
+        chain = bool(self.can_chain_dgrad(B) and not split and lowrank is None and B <= 32)
+        # conv weight/bias grads are accumulated with atomics across M-chunks: the fc dgrad launch
+        # zeroes that range in-kernel; fc grads are plain stores while B <= 32
+        return _StepFlags(split=bool(split), gnoise=gnoise, noisy=self.noisy and sg, defer=defer, dwg=dwg, det=det,
+                          chain=chain, zero_in_head=B <= 32 and not self.two_stream)
+
+    def _begin_step(self, online, target, batch, grad_out, noise, noise_target, acting) -> SimpleNamespace:
+        """Batch checks, workspace, packed / effective weights: the step's tensors and pointers."""
+        lay = self.layout
         frames = batch.get('frames')
         if frames is not None:             # slot batch: conv1 reads the replay frame ring directly
             s, ns = batch['state_slots'], batch['next_slots']
@@ -1253,248 +1299,272 @@ class HipExecutor:
         # noisy nets: effective weights under this step's noise (mixed + packed on the GPU)
         eo, et = self.effective(online, noise), self.effective(target, noise_target)
         ninst = 3 if self.double else 2
-        xs = [s, ns, ns][:ninst]
-        packs = [po, pt, po][:ninst]
-        flats = [eo, et, eo][:ninst]
+        E = 0
         if acting is not None:
             assert frames is not None and self.supports_fused_acting(), 'fused acting needs a slot batch'
             E = acting['stacks'].shape[0]
             assert acting['stacks'].dtype == torch.int32 and acting['stacks'].is_contiguous() and E <= B
-        # conv weight/bias grads are accumulated with atomics across M-chunks: the head
-        # kernel zeroes that range in-kernel; fc grads are plain stores while B <= 32
+        spec = batch.get('sample_spec')
+        if spec is not None:
+            assert self.fused_trunk and frames is not None, 'deferred sampling needs the fused trunk'
+        return SimpleNamespace(
+            B=B, dev=dev, ws=ws, s=s, frames=frames, po=po, eo=eo, ninst=ninst, acting=acting, E=E, grad=grad_out,
+            xs=[s, ns, ns][:ninst], packs=[po, pt, po][:ninst], flats=[eo, et, eo][:ninst],
+            sample=(spec, ninst) if spec is not None else None, fold=self.can_fold_head(B, E),
+            g=lambda n: grad_out.data_ptr() + 4 * lay.offsets[n],
+            pko=lambda key: po.data_ptr() + self.esz * self.poff[key])
+
+    def _forward(self, st, fl):
+        """Gradient zeroing (when the fc dgrad launch does not do it) and the trunk forward."""
+        lay, B, dev = self.layout, st.B, st.dev
         conv_lo = lay.offsets[self.arch.convs[0].name + '/w']
         conv_hi = max(lay.offsets[c.name + '/b'] + c.cout for c in self.arch.convs)
         conv_hi = (conv_hi + 3) // 4 * 4
-        zero_in_head = B <= 32 and not self.two_stream
+        st.zero = ([st.grad.data_ptr() + 4 * conv_lo, conv_hi - conv_lo] if fl.zero_in_head and not fl.det else [])
         # Two streams (= two parallel branches of the captured HIP graph):
         # main: forward -> head -> fc/conv3/conv2 dgrad chain (critical path)
         # side: grad zeroing (overlaps the forward) and every weight-gradient
         #       kernel, each gated on the dgrad output it consumes.
         # Measured on MI355X: the cross-stream waits cost more than the overlap
         # gains at B=32 (3.9k vs 4.5k steps/s), so the side branch is off by default.
-        main = torch.cuda.current_stream(dev)
-        side = self._side_stream(dev) if self.two_stream else main
-        if not zero_in_head:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                grad_out.zero_()
-            ev_zero = self._event('zero', side)
-        spec = batch.get('sample_spec')
-        if spec is not None:
-            assert self.fused_trunk and frames is not None, 'deferred sampling needs the fused trunk'
-        sample = (spec, ninst) if spec is not None else None
-        fold = self.can_fold_head(B, 0 if acting is None else E)
-        # the fc / conv3 / conv2 dgrads as one launch (single-process grouped-wgrad path); its
-        # counters are zeroed by this step's fc forward launch
-        chain = (self.can_chain_dgrad(B) and not split and lowrank is None and B <= 32
-                 and self.arch.network == 'nature')
-        self._fc_zero = self._chain_ws(B, dev) if chain else None
-        if acting is None:
-            self._fwd_trunk(xs, packs, flats, ws, B, ninst, frames=frames, sample=sample, fc=not fold)
+        st.main = torch.cuda.current_stream(dev)
+        st.side = self._side_stream(dev) if self.two_stream else st.main
+        if not fl.zero_in_head:
+            st.side.wait_stream(st.main)
+            with torch.cuda.stream(st.side):
+                st.grad.zero_()
+            ev_zero = self._event('zero', st.side)
+        # (the dgrad chain's counters are zeroed by this step's fc forward launch)
+        st.fc_zero = self._chain_ws(B, dev) if fl.chain else None
+        if st.acting is None:
+            self._fwd_trunk(st.xs, st.packs, st.flats, st.ws, B, st.ninst, frames=st.frames, sample=st.sample,
+                            fc=not st.fold, fc_zero=st.fc_zero)
         else:
-            self._fwd_trunk(xs + [acting['stacks']], packs + [po], flats + [eo], ws, B, ninst + 1, frames=frames,
-                            M=[B] * ninst + [E], sample=sample, fc=not fold)
-        if not zero_in_head:
-            main.wait_event(ev_zero)
-        det = bool(det_wgrad)
-        assert not det or (self.can_det_wgrad(B) and lowrank is None), 'det_wgrad: not available here'
-        zero = [grad_out.data_ptr() + 4 * conv_lo, conv_hi - conv_lo] if zero_in_head and not det else []
-        # ---- fused head + TD loss + head backward
-        w, b, wv, bv = self._head_ptrs(flats)
-        g = lambda n: grad_out.data_ptr() + 4 * lay.offsets[n]
+            self._fwd_trunk(st.xs + [st.acting['stacks']], st.packs + [st.po], st.flats + [st.eo], st.ws, B,
+                            st.ninst + 1, frames=st.frames, M=[B] * st.ninst + [st.E], sample=st.sample,
+                            fc=not st.fold, fc_zero=st.fc_zero)
+        if not fl.zero_in_head:
+            st.main.wait_event(ev_zero)
+
+    def _head_loss(self, st, fl, batch):
+        """Fused head + TD loss + head backward (scalar heads with the fold: + the fc forward)."""
+        ws, B, g, acting, ninst = st.ws, st.B, st.g, st.acting, st.ninst
+        w, b, wv, bv = self._head_ptrs(st.flats)
         if self.dueling:
-            dw, db, dwv, dbv = g('advantage/output/w'), g('advantage/output/b'), g('value/output/w'), \
-                g('value/output/b')
+            st.hgrads = g('advantage/output/w'), g('advantage/output/b'), g('value/output/w'), g('value/output/b')
         else:
-            dw, db, dwv, dbv = g('output/w'), g('output/b'), 0, 0
+            st.hgrads = g('output/w'), g('output/b'), 0, 0
         act = batch['actions']
         assert act.dtype == torch.int32 and act.numel() == B
         rew, done, gam = (batch['rewards'].contiguous(), batch['dones'].contiguous(),
                           batch['gammas'].contiguous())
         wts = batch.get('weights')
-        self._c51_dev = dev
         hints = [B, self.A, self.HID, int(self.dueling), int(self.huber), 0]
         hio = [act.data_ptr(), rew.data_ptr(), done.data_ptr(), gam.data_ptr(),
                wts.data_ptr() if wts is not None else 0, ws['loss'].data_ptr(), ws['prio'].data_ptr(),
-               ws['q'].data_ptr() if not self.dist else 0, dw, db, dwv, dbv, ws['dh'].data_ptr()]
+               ws['q'].data_ptr() if not self.dist else 0, *st.hgrads, ws['dh'].data_ptr()]
         hactor = [] if acting is None else list(acting['ptrs']) + list(acting['ints'])
         hactor_f = [] if acting is None else list(acting['f'])
         act_h = 0 if acting is None else ws['h'][ninst].data_ptr()
-        if fold:
+        if st.fold:
             # fc forward + output layer + TD loss + dQ / dH (+ the fused acting step): one launch
-            self._fc_head(packs if acting is None else packs + [po], ws, B, ninst, hints, w, b, wv, bv, hio,
-                          hactor, hactor_f, act_h, dev)
+            self._fc_head(st.packs if acting is None else st.packs + [st.po], ws, B, ninst, hints, w, b, wv, bv, hio,
+                          hactor, hactor_f, act_h, st.dev, fc_zero=st.fc_zero)
         else:
             self._head(hints, [ws['h'][i].data_ptr() for i in range(ninst)], w, b, wv, bv, hio,
-                       *self._head_packs(packs), [],          # (the conv grad range is zeroed by the fc dgrad)
+                       *self._head_packs(st.packs), [],       # (the conv grad range is zeroed by the fc dgrad)
                        hactor, hactor_f, act_h=act_h, ws=ws)
-        self._fc_zero = None                # (consumed by this step's fc forward launch)
-        # ---- backward (online instance 0 only)
-        c1, c2, c3 = self.arch.convs
-        (h1, w1), (h2, w2), (h3, w3) = c1.out_hw, c2.out_hw, c3.out_hw
-        H, HH, F = self.HID, self.HH, self.FLAT
-        pko = lambda key: po.data_ptr() + self.esz * self.poff[key]
-        if self.dueling:
-            fw, fb, fw2, fb2 = g('value/fcl/w'), g('value/fcl/b'), g('advantage/fcl/w'), g('advantage/fcl/b')
-        else:
-            fw, fb, fw2, fb2 = g('fcl/w'), g('fcl/b'), 0, 0
-        # fc dgrad (+ the scalar head's backward: dH, dW_out, db_out from the head's dQ)
-        hmembers, hdims = self._head_wgrad_members(ws, B, ws['h'][0].data_ptr(), (dw, db, dwv, dbv))
-        fc_dgrad = lambda: self._fc_dgrad(ws, B, po, zero, draw_noise)
-        if self.arch.network == 'cnn':
-            defer = bool(defer_fc) and self.can_defer_fc(B, gnoise is not None)
-            assert defer or not defer_fc, 'defer_fc: not available for this executor / batch'
-            dwg = bool(defer_wgrad)
-            assert not dwg or (defer and not split and self.can_defer_wgrad(B, gnoise is not None)), \
-                'defer_wgrad (cnn): needs defer_fc, one process'
-            out = self._cnn_backward(ws, B, s, frames, po, g, fw, fb, fw2, fb2, grad_out, gnoise, dev, fc_dgrad,
-                                     hmembers, hdims, defer=defer, defer_wgrad=dwg)
-            return out + (None,) if split else out
-        x1, x2, x3 = ws['x1'][0].data_ptr(), ws['x2'][0].data_ptr(), ws['x3'][0].data_ptr()
-        mc_fc = (B + 31) // 32 * 32
-        K1, K2, K3 = c1.k * c1.k * c1.cin, c2.k * c2.k * c2.cin, c3.k * c3.k * c3.cin
-        d1 = [B * h1 * w1, c1.cout, K1, 0, 0, 84, 84, h1, w1, 0, 0]
-        kind1 = _KIND['C1']
+
+    # ----------------------------------------------------------- backward (online instance 0 only)
+    def _conv_member(self, i, c, x, dz, st, in_hw, out_hw, pad=(0, 0), frames=None):
+        """Weight-gradient (member, dims) of conv layer i: dW = patches(x)^T dz over the B * out_hw
+        output positions (``frames``: conv1 reading its patches from the replay frame ring through
+        the slot table ``x``)."""
+        dims = [st.B * out_hw[0] * out_hw[1], c.cout, c.k * c.k * c.cin, 0, 0, *in_hw, *out_hw, *pad]
         if frames is not None:
-            d1 += [frames.data_ptr(), 84 * 84]
-            kind1 = _KIND['F1']
+            dims += [frames.data_ptr(), 84 * 84]
+        kind = _KIND['F1'] if frames is not None else _KIND['C%d' % i]
+        return [kind, x, dz, c.cout, st.g(c.name + '/w'), st.g(c.name + '/b'), 0, 0, c.cout, c.cout], dims
+
+    def _fc_member(self, st, x, dh, rows, kind='DFWD'):
+        """Weight-gradient (member, dims) of the hidden dense layer(s): dW[F][HH] = x^T dh, db = sum dh."""
+        g = st.g
+        if self.dueling:
+            fg = g('value/fcl/w'), g('value/fcl/b'), g('advantage/fcl/w'), g('advantage/fcl/b')
+        else:
+            fg = g('fcl/w'), g('fcl/b'), 0, 0
+        return ([_KIND[kind], x, dh, self.HH, *fg, self.HID, self.HH],
+                [rows, self.HH, self.FLAT, 0, 0, 0, 0, 0, 0, 0, 0])
+
+    def _group(self, pairs, scale0=1.0):
+        """(members, dims, scales) of a grouped weight-gradient launch (conv1, when in it, comes first:
+        the input scale is folded into its gradient)."""
+        return [m for m, _ in pairs], [d for _, d in pairs], [scale0] + [1.0] * (len(pairs) - 1)
+
+    def _wgrad(self, pair, mc, a, b, scale=1.0, atomic=True, **kw):
+        """One member as a launch of its own."""
+        m, dims = pair
+        self.ext.qnet_wgrad(m[0], m[1], dims, *m[2:], mc, a, b, scale, atomic, **kw)
+
+    def _sigma_grads(self, st, fl):
+        """dL/dsigma from dL/dW_eff (in the mu slots) under the step's noise."""
+        if fl.noisy:
+            self.ext.qnet_noisy_grad(st.grad.data_ptr(), fl.gnoise.data_ptr(), self._noisy_jobs_on(st.dev).data_ptr(),
+                                     len(self.noisy_jobs), self._noisy_max)
+
+    def _conv_dgrad(self, st, i):
+        """dz_{i-1} = (dz_i W_i^T) * (x_{i-1} > 0) on the igemm kernel (conv i's packed dgrad fragments)."""
+        ws = st.ws
+        self.ext.qnet_igemm(_KIND['D%d' % i], [ws['dz%d' % i].data_ptr()], [st.pko('conv%d/dgrad' % i)], [],
+                            [ws['dz%d' % (i - 1)].data_ptr()], [ws['x%d' % (i - 1)][0].data_ptr()], [1.0],
+                            self._conv_dgrad_dims(st.B, i))
+
+    def _conv_dgrad_dims(self, B, i):
+        c, (hi, wi), (ho, wo) = self.arch.convs[i - 1], self.arch.convs[i - 2].out_hw, self.arch.convs[i - 1].out_hw
+        return [B * hi * wi, c.cin, c.k * c.k * c.cout, c.cin // 16, c.cin, hi, wi, ho, wo, 0, 0]
+
+    def _nature_members(self, st):
+        """The Nature backward's (member, dims) pairs: [conv1, conv3, conv2] (conv1 first: the longest
+        member), the fc layer, the output layer."""
+        c1, c2, c3 = self.arch.convs
+        ws = st.ws
+        convs = [self._conv_member(1, c1, st.s.data_ptr(), ws['dz1'].data_ptr(), st, (84, 84), c1.out_hw,
+                                   frames=st.frames),
+                 self._conv_member(3, c3, ws['x2'][0].data_ptr(), ws['dz3'].data_ptr(), st, c2.out_hw, c3.out_hw),
+                 self._conv_member(2, c2, ws['x1'][0].data_ptr(), ws['dz2'].data_ptr(), st, c1.out_hw, c2.out_hw)]
+        # fc dgrad (+ the scalar head's backward: dH, dW_out, db_out from the head's dQ)
+        return (convs, self._fc_member(st, ws['x3'][0].data_ptr(), ws['dh'].data_ptr(), st.B),
+                self._head_wgrad_members(ws, st.B, ws['h'][0].data_ptr(), st.hgrads))
+
+    def _backward(self, st, fl, draw_noise, lowrank):
+        """Launch the backward into ``st.grad``; returns the split step's ``tail`` (None: nothing is
+        left to launch). Two strategies: the grouped path, or one launch per layer over two streams."""
         # (fc wgrad members are plain stores only while one 32-row M-chunk covers the batch)
-        if self.grouped_wgrad and not self.two_stream and B <= 32:
-            # dgrad chain: dz3 = (dh W_fc^T)*(x3>0) -> dz2 -> dz1, then ONE grouped launch for
-            # the four weight gradients (conv1 first: the longest member)
-            members = [[kind1, s.data_ptr(), ws['dz1'].data_ptr(), c1.cout, g('conv1/w'), g('conv1/b'), 0, 0,
-                        c1.cout, c1.cout],
-                       [_KIND['C3'], x2, ws['dz3'].data_ptr(), c3.cout, g('conv3/w'), g('conv3/b'), 0, 0, c3.cout,
-                        c3.cout],
-                       [_KIND['C2'], x1, ws['dz2'].data_ptr(), c2.cout, g('conv2/w'), g('conv2/b'), 0, 0, c2.cout,
-                        c2.cout],
-                       [_KIND['DFWD'], x3, ws['dh'].data_ptr(), HH, fw, fb, fw2, fb2, H, HH]] + hmembers
-            dims = [d1, [B * h3 * w3, c3.cout, K3, 0, 0, h2, w2, h3, w3, 0, 0],
-                    [B * h2 * w2, c2.cout, K2, 0, 0, h1, w1, h2, w2, 0, 0], [B, HH, F, 0, 0, 0, 0, 0, 0, 0, 0]] + hdims
-            scales = [self.input_scale] + [1.0] * (len(members) - 1)
-            if det:
-                pl = self._det_plan(B, dev)
-                for m, c in zip(members[:3], (c1, c3, c2)):
-                    m += self._det_member(pl, c.name)
-                self._parts_pending = (pl['jobs'], pl['buf'].data_ptr())
-            noisy = self.noisy and gnoise is not None
-            defer = bool(defer_fc) and self.can_defer_fc(B, gnoise is not None)
-            assert defer or not defer_fc, 'defer_fc: not available for this executor / batch'
-            dwg = bool(defer_wgrad)
-            assert not dwg or (defer and not det and self.can_defer_wgrad(B, gnoise is not None)
-                               and (not split or (lowrank is not None and self.dp_exchange is not None))), \
-                'defer_wgrad: needs defer_fc, no det_wgrad; under DP the low-rank exchange and dp_exchange'
-            if defer and not (split and lowrank is not None):
-                # the optimizer launch forms dW_fc = x3^T dH from this rank's rows
-                self._fc_pending = (x3, ws['dh'].data_ptr(), B)
-                members, dims, scales = members[:3] + members[4:], dims[:3] + dims[4:], scales[:3] + scales[4:]
-            if split and not noisy and lowrank is not None:
-                # (noisy nets reach here only with the sigma gradients left to the fused optimizer)
-                assert self.lowrank_spec(B, sigma_fused=True) is not None, 'low-rank exchange not available here'
-                W, rk = int(lowrank['world']), int(lowrank['rank'])
-                lw = self._lowrank_ws(B, W, dev)
-                if self.dist:                              # C51: dH = dlogits [W | Wv]^T * (h > 0) first
-                    self._c51_dh(ws, B, po)
-                # in stream order (a graph fork / join costs ~25 us on this ROCm: measured,
-                # scripts/probe_graph_concurrency.py), right after the head: x3 and dh are final.
-                # The all-gather runs as a side duty of the fc dgrad launch (its own grid.z slice)
-                # when the transport can hand out device args; else as its own launch first.
-                seg = ([x3, ws['dh'].data_ptr()], [lw['x'].data_ptr(), lw['dh'].data_ptr()],
-                       [B * F * self.esz, B * HH * self.esz])
-                ga = None
-                if lowrank.get('gather_args') is not None:
-                    dev_args, nblk = lowrank['gather_args'](*seg)      # (cached by the transport)
-                    ga = (dev_args.data_ptr(), nblk)
-                    self._fc_dgrad(ws, B, po, zero, draw_noise, dh_done=True, gather=ga)
-                else:
-                    lowrank['gather'](*seg)
-                if defer:
-                    # the optimizer launch forms dW_fc and the fc bias gradient from all W*B rows
-                    self._fc_pending = (lw['x'].data_ptr(), lw['dh'].data_ptr(), W * B)
-                else:
-                    # sum over all W*B rows in one block per weight tile (64-row chunks in a fixed
-                    # order, no atomics: bit-identical on every rank)
-                    ext.qnet_wgrad(_KIND['DLR'], lw['x'].data_ptr(), [W * B, HH, F, 0, 0, 0, 0, 0, 0, 0, 0],
-                                   lw['dh'].data_ptr(), HH, fw, fb, fw2, fb2, H, HH, 64, 64, 128, 1.0, False,
-                                   mloop=(W * B + 63) // 64, db_zero=rk != 0)
-                if ga is None:
-                    self._fc_dgrad(ws, B, po, zero, draw_noise, dh_done=True)
-                # the output layer's members join the conv members in the tail's grouped launch
-                members, dims, scales = members[:3] + members[4:], dims[:3] + dims[4:], scales[:3] + scales[4:]
-            elif split and not noisy:
-                assert not defer, 'defer_fc under data parallelism needs the low-rank exchange'
-                fc_dgrad()
-                # dense weight gradients now (they need only dh, dQ and x3 / h): the dense range is final
-                ext.qnet_wgrad_group(members[3:], dims[3:], scales[3:])
-                members, dims, scales = members[:3], dims[:3], scales[:3]
-            elif not chain:
-                fc_dgrad()
-            d3 = [B * h2 * w2, c3.cin, c3.k * c3.k * c3.cout, c3.cin // 16, c3.cin, h2, w2, h3, w3, 0, 0]
-            d2 = [B * h1 * w1, c2.cin, c2.k * c2.k * c2.cout, c2.cin // 16, c2.cin, h1, w1, h2, w2, 0, 0]
+        if self.grouped_wgrad and not self.two_stream and st.B <= 32:
+            return self._backward_grouped(st, fl, draw_noise, lowrank)
+        return self._backward_streams(st, fl, draw_noise)
 
-            def tail():
-                if chain:
-                    # fc dgrad (+ its side duties) -> conv3 dgrad -> conv2 dgrad: ONE launch
-                    if self.dist:                   # C51: dH = dlogits [W | Wv]^T * (h > 0) first
-                        self._c51_dh(ws, B, po)
-                    dh, pk, dz3, x3m, dims0, aux0, auxf0 = self._fc_dgrad_args(ws, B, po, zero, draw_noise)
-                    three = self.chain_dgrad >= 2       # (2: the conv2 dgrad inside the chain too)
-                    ext.qnet_dgrad_chain(dh, pk, dz3, x3m, dims0, aux0, auxf0, pko('conv3/dgrad'),
-                                         ws['dz2'].data_ptr(), x2, d3, pko('conv2/dgrad'),
-                                         ws['dz1'].data_ptr() if three else 0, x1, d2,
-                                         self._chain_ws(B, dev).data_ptr(), B)
-                    if not three:
-                        ext.qnet_igemm(_KIND['D2'], [ws['dz2'].data_ptr()], [pko('conv2/dgrad')], [],
-                                       [ws['dz1'].data_ptr()], [x1], [1.0], d2)
-                else:
-                    ext.qnet_igemm(_KIND['D3'], [ws['dz3'].data_ptr()], [pko('conv3/dgrad')], [],
-                                   [ws['dz2'].data_ptr()], [x2], [1.0], d3)
-                    ext.qnet_igemm(_KIND['D2'], [ws['dz2'].data_ptr()], [pko('conv2/dgrad')], [],
-                                   [ws['dz1'].data_ptr()], [x1], [1.0], d2)
-                if dwg:                 # the next update_and_pack runs the group beside the fc update
-                    self._wg_pending = (members, dims, scales)
-                else:
-                    ext.qnet_wgrad_group(members, dims, scales)
-                if noisy:
-                    ext.qnet_noisy_grad(grad_out.data_ptr(), gnoise.data_ptr(), self._noisy_jobs_on(dev).data_ptr(),
-                                        len(self.noisy_jobs), self._noisy_max)
+    def _backward_grouped(self, st, fl, draw_noise, lowrank):
+        """dgrad chain: dz3 = (dh W_fc^T)*(x3>0) -> dz2 -> dz1, then ONE grouped launch for the
+        weight gradients that are not left to the optimizer launch."""
+        ws, B = st.ws, st.B
+        convs, fcm, heads = self._nature_members(st)
+        if fl.det:
+            pl = self._det_plan(B, st.dev)
+            c1, c2, c3 = self.arch.convs
+            for (m, _), c in zip(convs, (c1, c3, c2)):
+                m += self._det_member(pl, c.name)
+            self._pending.parts = (pl['jobs'], pl['buf'].data_ptr())
+        dense = [fcm] + heads              # the dense members a weight-gradient launch still computes
+        if fl.defer and not (fl.split and lowrank is not None):
+            # the optimizer launch forms dW_fc = x3^T dH from this rank's rows
+            self._pending.fc = (ws['x3'][0].data_ptr(), ws['dh'].data_ptr(), B)
+            dense = heads
+        if fl.split and not fl.noisy and lowrank is not None:
+            # (noisy nets reach here only with the sigma gradients left to the fused optimizer)
+            self._lowrank_fc(st, fl, draw_noise, lowrank)
+            # the output layer's members join the conv members in the tail's grouped launch
+            dense = heads
+        elif fl.split and not fl.noisy:
+            assert not fl.defer, 'defer_fc under data parallelism needs the low-rank exchange'
+            self._fc_dgrad(ws, B, st.po, st.zero, draw_noise)
+            # dense weight gradients now (they need only dh, dQ and x3 / h): the dense range is final
+            self.ext.qnet_wgrad_group(*self._group(dense))
+            dense = []
+        elif not fl.chain:
+            self._fc_dgrad(ws, B, st.po, st.zero, draw_noise)
+        group = self._group(convs + dense, self.input_scale)
 
-            if split and not noisy:
-                return ws['loss'], ws['prio'], tail
-            tail()
-            return (ws['loss'], ws['prio'], None) if split else (ws['loss'], ws['prio'])
+        def tail():
+            self._dgrad_tail(st, fl, draw_noise, group)
+
+        if fl.split and not fl.noisy:
+            return tail
+        tail()
+        return None
+
+    def _lowrank_fc(self, st, fl, draw_noise, lowrank):
+        """Data parallelism, low-rank exchange: all-gather the fc factors (x3, dH) of every rank and
+        form the summed fc gradient from all W*B rows (here, or -- defer_fc -- in the optimizer launch)."""
+        ws, B, po, F, HH = st.ws, st.B, st.po, self.FLAT, self.HH
+        assert self.lowrank_spec(B, sigma_fused=True) is not None, 'low-rank exchange not available here'
+        W, rk = int(lowrank['world']), int(lowrank['rank'])
+        lw = self._lowrank_ws(B, W, st.dev)
+        if self.dist:                              # C51: dH = dlogits [W | Wv]^T * (h > 0) first
+            self._c51_dh(ws, B, po)
+        # in stream order (a graph fork / join costs ~25 us on this ROCm: measured,
+        # scripts/probe_graph_concurrency.py), right after the head: x3 and dh are final.
+        # The all-gather runs as a side duty of the fc dgrad launch (its own grid.z slice)
+        # when the transport can hand out device args; else as its own launch first.
+        seg = ([ws['x3'][0].data_ptr(), ws['dh'].data_ptr()], [lw['x'].data_ptr(), lw['dh'].data_ptr()],
+               [B * F * self.esz, B * HH * self.esz])
+        ga = None
+        if lowrank.get('gather_args') is not None:
+            dev_args, nblk = lowrank['gather_args'](*seg)      # (cached by the transport)
+            ga = (dev_args.data_ptr(), nblk)
+            self._fc_dgrad(ws, B, po, st.zero, draw_noise, dh_done=True, gather=ga)
+        else:
+            lowrank['gather'](*seg)
+        if fl.defer:
+            # the optimizer launch forms dW_fc and the fc bias gradient from all W*B rows
+            self._pending.fc = (lw['x'].data_ptr(), lw['dh'].data_ptr(), W * B)
+        else:
+            # sum over all W*B rows in one block per weight tile (64-row chunks in a fixed
+            # order, no atomics: bit-identical on every rank)
+            self._wgrad(self._fc_member(st, lw['x'].data_ptr(), lw['dh'].data_ptr(), W * B, kind='DLR'), 64, 64, 128,
+                        atomic=False, mloop=(W * B + 63) // 64, db_zero=rk != 0)
+        if ga is None:
+            self._fc_dgrad(ws, B, po, st.zero, draw_noise, dh_done=True)
+
+    def _dgrad_tail(self, st, fl, draw_noise, group):
+        """[fc ->] conv3 -> conv2 dgrads, then the grouped weight-gradient launch (or its hand-off to
+        the optimizer launch) and the sigma gradients."""
+        ext, ws, B = self.ext, st.ws, st.B
+        if fl.chain:
+            # fc dgrad (+ its side duties) -> conv3 dgrad -> conv2 dgrad: ONE launch
+            if self.dist:                   # C51: dH = dlogits [W | Wv]^T * (h > 0) first
+                self._c51_dh(ws, B, st.po)
+            dh, pk, dz3, x3m, dims0, aux0, auxf0 = self._fc_dgrad_args(ws, B, st.po, st.zero, draw_noise)
+            three = self.chain_dgrad >= 2       # (2: the conv2 dgrad inside the chain too)
+            ext.qnet_dgrad_chain(dh, pk, dz3, x3m, dims0, aux0, auxf0, st.pko('conv3/dgrad'),
+                                 ws['dz2'].data_ptr(), ws['x2'][0].data_ptr(), self._conv_dgrad_dims(B, 3),
+                                 st.pko('conv2/dgrad'), ws['dz1'].data_ptr() if three else 0, ws['x1'][0].data_ptr(),
+                                 self._conv_dgrad_dims(B, 2), self._chain_ws(B, st.dev).data_ptr(), B)
+            if not three:
+                self._conv_dgrad(st, 2)
+        else:
+            self._conv_dgrad(st, 3)
+            self._conv_dgrad(st, 2)
+        if fl.dwg:                 # the next update_and_pack runs the group beside the fc update
+            self._pending.wg = group
+        else:
+            ext.qnet_wgrad_group(*group)
+        self._sigma_grads(st, fl)
+
+    def _backward_streams(self, st, fl, draw_noise):
+        """One launch per layer: the dgrads on the main stream, every weight gradient on the side
+        stream (``two_stream``; else the same stream), each gated on the dgrad output it consumes."""
+        ws, B, main, side = st.ws, st.B, st.main, st.side
+        (conv1, conv3, conv2), fcm, heads = self._nature_members(st)
         # fc dgrad: dz3 = (dh W^T) * (x3 > 0) (scalar heads: dh itself is built in this launch)
-        fc_dgrad()
+        self._fc_dgrad(ws, B, st.po, st.zero, draw_noise)
         side.wait_event(self._event('dz3', main))
         with torch.cuda.stream(side):
-            # fc wgrad: dW[F][HH] = x3^T dh, db = sum dh
-            ext.qnet_wgrad(_KIND['DFWD'], x3, [B, HH, F, 0, 0, 0, 0, 0, 0, 0, 0], ws['dh'].data_ptr(), HH,
-                           fw, fb, fw2, fb2, H, HH, mc_fc, 64, 128, 1.0, False)
-            for m, d in zip(hmembers, hdims):           # output layer (B > 32: atomics on the zeroed grad)
-                ext.qnet_wgrad(m[0], m[1], d, m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], 32, 64, 64, 1.0, True)
+            self._wgrad(fcm, (B + 31) // 32 * 32, 64, 128, atomic=False)
+            for pair in heads:                          # output layer (B > 32: atomics on the zeroed grad)
+                self._wgrad(pair, 32, 64, 64)
         with torch.cuda.stream(side):
-            ext.qnet_wgrad(_KIND['C3'], x2, [B * h3 * w3, c3.cout, K3, 0, 0, h2, w2, h3, w3, 0, 0],
-                           ws['dz3'].data_ptr(), c3.cout, g('conv3/w'), g('conv3/b'), 0, 0, c3.cout, c3.cout,
-                           128, 192, 64, 1.0, True)
-        ext.qnet_igemm(_KIND['D3'], [ws['dz3'].data_ptr()], [pko('conv3/dgrad')], [], [ws['dz2'].data_ptr()], [x2],
-                       [1.0], [B * h2 * w2, c3.cin, c3.k * c3.k * c3.cout, c3.cin // 16, c3.cin, h2, w2, h3, w3,
-                               0, 0])
+            self._wgrad(conv3, 128, 192, 64)
+        self._conv_dgrad(st, 3)
         side.wait_event(self._event('dz2', main))
         with torch.cuda.stream(side):
-            ext.qnet_wgrad(_KIND['C2'], x1, [B * h2 * w2, c2.cout, K2, 0, 0, h1, w1, h2, w2, 0, 0],
-                           ws['dz2'].data_ptr(), c2.cout, g('conv2/w'), g('conv2/b'), 0, 0, c2.cout, c2.cout,
-                           128, 128, 64, 1.0, True)
-        ext.qnet_igemm(_KIND['D2'], [ws['dz2'].data_ptr()], [pko('conv2/dgrad')], [], [ws['dz1'].data_ptr()], [x1],
-                       [1.0], [B * h1 * w1, c2.cin, c2.k * c2.k * c2.cout, c2.cin // 16, c2.cin, h1, w1, h2, w2,
-                               0, 0])
+            self._wgrad(conv2, 128, 128, 64)
+        self._conv_dgrad(st, 2)
         # conv1: wgrad only (input scale folded in); last kernel of the step, on main
-        ext.qnet_wgrad(kind1, s.data_ptr(), d1, ws['dz1'].data_ptr(), c1.cout, g('conv1/w'), g('conv1/b'), 0, 0,
-                       c1.cout, c1.cout, 128, 256, 32, self.input_scale, True)
-        if self.noisy and gnoise is not None:      # dL/dsigma from dL/dW_eff (in the mu slots)
-            ext.qnet_noisy_grad(grad_out.data_ptr(), gnoise.data_ptr(), self._noisy_jobs_on(dev).data_ptr(),
-                                len(self.noisy_jobs), self._noisy_max)
+        self._wgrad(conv1, 128, 256, 32, scale=self.input_scale)
+        self._sigma_grads(st, fl)
         main.wait_stream(side)
-        return (ws['loss'], ws['prio'], None) if split else (ws['loss'], ws['prio'])
+        return None
 
 
 class HipCnnExecutor(HipExecutor):
@@ -1528,7 +1598,8 @@ class HipCnnExecutor(HipExecutor):
         self._ws[key] = ws
         return ws
 
-    def _fwd_trunk(self, xs, packs, flats, ws, B, ninst, frames=None, keep_acts=True, M=(), sample=None, fc=True):
+    def _fwd_trunk(self, xs, packs, flats, ws, B, ninst, frames=None, keep_acts=True, M=(), sample=None, fc=True,
+                   fc_zero=None):
         assert sample is None, 'the cnn forward reads sampler-made slot tables'
         lay = self.layout
         pad = lambda v: list(v) + [0] * (4 - len(v))
@@ -1544,55 +1615,41 @@ class HipCnnExecutor(HipExecutor):
         self.ext.qnet_cnn_fwd(frames.data_ptr() if frames is not None else 0, ptrs, B, ninst, self.input_scale,
                               list(M), prof=prof)
         if fc:
-            self._fc_fwd(packs, flats, ws, B, ninst)
+            self._fc_fwd(packs, flats, ws, B, ninst, fc_zero)
 
-    def _cnn_backward(self, ws, B, s, frames, po, g, fw, fb, fw2, fb2, grad_out, noise, dev, fc_dgrad,
-                      hmembers=(), hdims=(), defer=False, defer_wgrad=False):
-        ext = self.ext
-        F, HH, H = self.FLAT, self.HH, self.HID
-        pko = lambda key: po.data_ptr() + self.esz * self.poff[key]
-        x3 = ws['x3'][0].data_ptr()
+    _defer_wgrad_needs = 'defer_wgrad (cnn): needs defer_fc, one process'
+
+    def _backward(self, st, fl, draw_noise, lowrank):
+        assert not (fl.dwg and fl.split), self._defer_wgrad_needs     # (``lowrank`` is not used here)
+        ext, ws, B = self.ext, st.ws, st.B
         # dp3 = (dh W_fc^T) * (pooled conv3 output > 0)
-        fc_dgrad()
+        self._fc_dgrad(ws, B, st.po, st.zero, draw_noise)
         # pool / ReLU / conv dgrad chain per sample -> d(conv pre-activations)
         ext.qnet_cnn_bwd([ws['dz3'].data_ptr(), ws['a1'].data_ptr(), ws['a2'].data_ptr(), ws['a3'].data_ptr(),
-                          pko('conv3/dgrad'), pko('conv2/dgrad'), ws['dc1'].data_ptr(), ws['dc2'].data_ptr(),
+                          st.pko('conv3/dgrad'), st.pko('conv2/dgrad'), ws['dc1'].data_ptr(), ws['dc2'].data_ptr(),
                           ws['dc3'].data_ptr()], B,
                          prof=self.cnn_prof[1].data_ptr() if self.cnn_prof is not None else 0,
                          parts=self.tuning.cnn_parts(self.compute_dtype))
         c1, c2, c3 = self.arch.convs
-        t1, _, l1, _ = c1.pads()
-        t2, _, l2, _ = c2.pads()
-        t3, _, l3, _ = c3.pads()
-        d1 = [B * 441, c1.cout, c1.k * c1.k * c1.cin, 0, 0, 84, 84, 21, 21, t1, l1]
-        kind1 = _KIND['C1']
-        if frames is not None:
-            d1 += [frames.data_ptr(), 84 * 84]
-            kind1 = _KIND['F1']
-        members = [[kind1, s.data_ptr(), ws['dc1'].data_ptr(), c1.cout, g('conv1/w'), g('conv1/b'), 0, 0, c1.cout,
-                    c1.cout],
-                   [_KIND['C3'], ws['p2'].data_ptr(), ws['dc3'].data_ptr(), c3.cout, g('conv3/w'), g('conv3/b'), 0, 0,
-                    c3.cout, c3.cout],
-                   [_KIND['C2'], ws['p1'].data_ptr(), ws['dc2'].data_ptr(), c2.cout, g('conv2/w'), g('conv2/b'), 0, 0,
-                    c2.cout, c2.cout]]
-        dims = [d1, [B * 9, c3.cout, c3.k * c3.k * c3.cin, 0, 0, 3, 3, 3, 3, t3, l3],
-                [B * 36, c2.cout, c2.k * c2.k * c2.cin, 0, 0, 11, 11, 6, 6, t2, l2]]
-        if defer:                       # dW_fc = x3^T dH inside the optimizer launch
-            self._fc_pending = (x3, ws['dh'].data_ptr(), B)
+        pad = lambda c: (c.pads()[0], c.pads()[2])          # (top, left) of the SAME padding
+        # conv2 / conv3 read the pooled activations
+        pairs = [self._conv_member(1, c1, st.s.data_ptr(), ws['dc1'].data_ptr(), st, (84, 84), (21, 21), pad(c1),
+                                   frames=st.frames),
+                 self._conv_member(3, c3, ws['p2'].data_ptr(), ws['dc3'].data_ptr(), st, (3, 3), (3, 3), pad(c3)),
+                 self._conv_member(2, c2, ws['p1'].data_ptr(), ws['dc2'].data_ptr(), st, (11, 11), (6, 6), pad(c2))]
+        x3 = ws['x3'][0].data_ptr()
+        if fl.defer:                    # dW_fc = x3^T dH inside the optimizer launch
+            self._pending.fc = (x3, ws['dh'].data_ptr(), B)
         else:
-            members.append([_KIND['DFWD'], x3, ws['dh'].data_ptr(), HH, fw, fb, fw2, fb2, H, HH])
-            dims.append([B, HH, F, 0, 0, 0, 0, 0, 0, 0, 0])
-        members += list(hmembers)
-        dims += list(hdims)
-        scales = [self.input_scale] + [1.0] * (len(members) - 1)
-        if defer_wgrad:                 # the next update_and_pack runs the group beside the fc update
-            self._wg_pending = (members, dims, scales)
+            pairs.append(self._fc_member(st, x3, ws['dh'].data_ptr(), B))
+        pairs += self._head_wgrad_members(ws, B, ws['h'][0].data_ptr(), st.hgrads)
+        group = self._group(pairs, self.input_scale)
+        if fl.dwg:                      # the next update_and_pack runs the group beside the fc update
+            self._pending.wg = group
         else:
-            ext.qnet_wgrad_group(members, dims, scales)
-        if self.noisy and noise is not None:
-            ext.qnet_noisy_grad(grad_out.data_ptr(), noise.data_ptr(), self._noisy_jobs_on(dev).data_ptr(),
-                                len(self.noisy_jobs), self._noisy_max)
-        return ws['loss'], ws['prio']
+            ext.qnet_wgrad_group(*group)
+        self._sigma_grads(st, fl)
+        return None
 
 
 def make_hip_executor(arch, layout, **kw):

@@ -49,7 +49,7 @@ def main():
                                target=net.target.flat, target_freq=1 << 30,
                                next_sample=spec if sampler else None, fc=fc if fused else None)
             if not fused:
-                ex._fc_pending = None
+                ex.take_pending_fc()
 
         def timeit(fn):
             for _ in range(10):
@@ -72,7 +72,7 @@ def main():
         out['fc_fused+sampler'] = timeit(lambda: launch(True, True))
         # the launch without the fc weight tiles (what remains if they run elsewhere)
         items_all = ex.upd_items
-        ex.upd_items = [it for it in items_all if not (it[0] == 0 and it[20] >= 0)]
+        ex.upd_items = [it for it in items_all if not (it.kind == 0 and it.fc_col >= 0)]
         ex._upd_dev = {}
         out['no_fc_tiles+sampler'] = timeit(lambda: launch(True, True))
         out['jobs_no_fc_tiles'] = len(ex.upd_items)

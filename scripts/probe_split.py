@@ -1,4 +1,4 @@
-"""Probe: the fused weight-gradient + optimizer launch (executor._update_split) of the flagship
+"""Probe: the fused weight-gradient + optimizer launch (executor.update_and_pack) of the flagship
 step, timed alone (HIP events over back-to-back launches):
 
   wgrad_group      the grouped weight-gradient launch it replaces (256-row chunks)
@@ -41,17 +41,19 @@ def main():
     assert learner._defer_wgrad, 'the split update is not active for this config'
     ex = net.executor
     seen = {}
-    orig = ex._update_split
+    orig = ex.update_and_pack
 
     def spy(*a, **k):
-        seen['wg'], seen['fc'] = ex._wg_pending, ex._fc_pending
+        pend = ex.snapshot_pending()
+        if pend.wg is not None:                 # (only the fused weight-gradient + update launch)
+            seen['wg'], seen['fc'] = pend.wg, pend.fc
         return orig(*a, **k)
 
-    ex._update_split = spy
+    ex.update_and_pack = spy
     for _ in range(3):
         learner.step()
     torch.cuda.synchronize()
-    ex._update_split = orig
+    del ex.update_and_pack
     wg, fc = seen['wg'], seen['fc']
     members, dims, scales = wg
     opt = net.optimizer

@@ -261,3 +261,27 @@ def test_lowrank_dense_wgrad_matches_fp32(W):
     run(True)
     torch.cuda.synchronize()
     assert torch.equal(dw, w1) and bool((db == 0).all())
+
+
+def test_optim_pack_refuses_a_mode_it_does_not_build():
+    """``target_noise`` without ``noise`` would be mode 2 (a target mix without a noisy net), which no
+    build instantiates. Through the binding it is the argument check "target mix needs target, noise,
+    teff, tpk" that refuses it, before the launcher is called -- so this test pins that the call
+    raises and touches nothing, not the launcher's own refusal of an unlisted mode, which no call
+    through the binding can reach (tests/test_ext_variants.py calls the launcher directly for that)."""
+    from dist_dqn_amd.ops import _ext
+    ext = _ext.load(required=True)
+    n = 2048
+    f32 = lambda k: torch.zeros(k, device=DEV)
+    w, grad, tgt = f32(n), torch.ones(n, device=DEV), f32(n)
+    step = torch.zeros(1, dtype=torch.int64, device=DEV)
+    row = [0] * ext.UPD_JOB_INTS           # one elementwise chunk over the whole buffer (never read)
+    row[0], row[2] = 1, n
+    jobs = torch.tensor(row, dtype=torch.int32, device=DEV)
+    pk = lambda: torch.zeros(256, dtype=torch.bfloat16, device=DEV)
+    with pytest.raises(RuntimeError, match='target mix needs'):
+        ext.optim_pack(0, w, grad, f32(n), f32(n), f32(2), torch.zeros(17 * 32, dtype=torch.int32, device=DEV), 0.1, 0.0,
+                       0, 1.0, step, [0.0] * 9, jobs, pk(), tgt, pk(), 1, 2048, None, None, None, None, [], [], [],
+                       f32(64), f32(n), pk(), None, [], 0)
+    torch.cuda.synchronize()
+    assert int(step) == 0 and not w.any() and not tgt.any()
