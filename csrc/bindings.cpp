@@ -2,11 +2,9 @@
 // (device, dtype, contiguity, shapes the kernels assume) and launches on the
 // current HIP stream, so the ops are captured correctly into HIP graphs.
 #include <cstring>
-#include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "bind_common.h"
 #include "include/dqn_act.h"
 #include "include/dqn_host.h"
 #include "include/dqn_kernels.h"
@@ -15,8 +13,6 @@
 
 namespace {
 
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
-
 #define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be a GPU tensor")
 #define CHECK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 #define CHECK_DT(t, dt) TORCH_CHECK((t).scalar_type() == (dt), #t " has wrong dtype: ", (t).scalar_type())
@@ -24,8 +20,6 @@ hipStream_t cur_stream() { return c10::hip::getCurrentHIPStreamMasqueradingAsCUD
 
 template <typename T>
 T* ptr(const torch::Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
-template <class T>
-T P(int64_t v) { return reinterpret_cast<T>(static_cast<intptr_t>(v)); }
 
 // [] or [state_idx, next_idx, actions, rewards, dones, gammas, a_out, r_out, d_out, g_out, st_slots, nx_slots]
 SampleOut sample_out(const std::vector<torch::Tensor>& v, int64_t B) {
@@ -140,188 +134,190 @@ void optimizer_step(int64_t op, torch::Tensor w, torch::Tensor grad, torch::Tens
                         (int)target_freq, cur_stream());
 }
 
-// optimizer step fused with the executor's weight packing (optim.hip optim_pack_kernel)
+// ---- optim_pack: the optimizer step fused with the executor's weight packing (optim.hip
+// optim_pack_kernel). OptimPackArgs (dqn_kernels.h) documents the arguments; each helper below
+// checks one group of them and fills its fields.
+using OptTensor = c10::optional<torch::Tensor>;
+bool given(const OptTensor& t) { return t.has_value() && t->defined(); }
+constexpr auto kActDtype = DQN_ACT_F32 ? torch::kFloat32 : DQN_ACT_F16 ? torch::kHalf : torch::kBFloat16;
+
+void opk_target(OptimPackArgs& a, const OptTensor& target, const OptTensor& target_packed, int64_t target_freq,
+                int64_t tsg, const torch::Tensor& w, const torch::Tensor& packed) {
+  if (given(target)) {
+    CHECK_T((*target), torch::kFloat32);
+    TORCH_CHECK(target->numel() == w.numel() && target_freq >= 1, "optim_pack: target sync args");
+    a.tgt = ptr<float>(*target);
+    if (given(target_packed)) {   // noisy nets: fp32 target only
+      TORCH_CHECK(target_packed->numel() == packed.numel(), "optim_pack: target packed size");
+      a.tgt_packed = target_packed->data_ptr();
+    }
+  }
+  TORCH_CHECK(a.op >= 0 || a.tgt == nullptr, "optim_pack: mix-only call with a target");
+  a.tfreq = (int)target_freq;
+  a.tsg = P<void*>(tsg);
+}
+
+// (after opk_target: the target mix needs a.tgt)
+void opk_noise(OptimPackArgs& a, const OptTensor& noise, const OptTensor& eff, const OptTensor& grad_noise,
+               const OptTensor& noise_dst, const OptTensor& noise_rng, const OptTensor& tnoise, const OptTensor& teff,
+               const OptTensor& tpk, const torch::Tensor& w, const torch::Tensor& packed) {
+  if (given(noise)) {
+    CHECK_T((*noise), torch::kFloat32);
+    a.noise = ptr<float>(*noise);
+  }
+  if (given(eff)) {
+    CHECK_T((*eff), torch::kFloat32);
+    TORCH_CHECK(eff->numel() == w.numel(), "optim_pack: eff size");
+    a.eff = ptr<float>(*eff);
+  }
+  if (given(grad_noise)) {
+    CHECK_T((*grad_noise), torch::kFloat32);
+    TORCH_CHECK(a.noise != nullptr && grad_noise->numel() == noise->numel(), "optim_pack: grad_noise size");
+    a.gnoise = ptr<float>(*grad_noise);
+  }
+  if (given(noise_dst)) {
+    CHECK_T((*noise_dst), torch::kFloat32);
+    TORCH_CHECK(a.op >= 0 && a.noise != nullptr && noise_dst->numel() == noise->numel() &&
+                noise_dst->data_ptr() != noise->data_ptr(), "optim_pack: noise_dst");
+    a.noise_dst = ptr<float>(*noise_dst);
+    a.noise_n = (int)noise_dst->numel();
+  }
+  if (given(noise_rng)) {
+    CHECK_T((*noise_rng), torch::kInt64);
+    TORCH_CHECK(a.op >= 0 && noise_rng->numel() >= 2, "optim_pack: noise_rng = [seed, counter] (update calls)");
+    a.noise_rng = ptr<int64_t>(*noise_rng);
+  }
+  if (given(tnoise)) {
+    CHECK_T((*tnoise), torch::kFloat32);
+    TORCH_CHECK(a.op >= 0 && a.tgt != nullptr && a.noise != nullptr && tnoise->numel() == noise->numel() &&
+                given(teff) && given(tpk), "optim_pack: target mix needs target, noise, teff, tpk");
+    CHECK_T((*teff), torch::kFloat32);
+    CHECK_T((*tpk), kActDtype);
+    TORCH_CHECK(teff->numel() == w.numel() && tpk->numel() == packed.numel() && tpk->data_ptr() != packed.data_ptr(),
+                "optim_pack: teff / tpk sizes");
+    a.tnoise = ptr<float>(*tnoise);
+    a.teff = ptr<float>(*teff);
+    a.tpk = tpk->data_ptr();
+  }
+}
+
+// sample: [] or 16 pointers (TrunkSample order) + B
+void opk_sample(OptimPackArgs& a, dqn::TrunkSample& smp, const std::vector<int64_t>& sample) {
+  if (sample.empty()) return;
+  TORCH_CHECK(a.op >= 0 && sample.size() == 17, "optim_pack sample: 16 pointers + B (update calls only)");
+  smp = trunk_sample(sample, "optim_pack");
+  smp.B = (int)sample[16];
+  TORCH_CHECK(smp.B >= 1 && smp.B <= 512, "optim_pack sample: 1 <= B <= 512 (one lane per sample)");
+  a.smp = &smp;
+}
+
+// per_p: [] or [sum, min, max_p, P, levels, upd_idx, upd_td, rng, size, step, idx_out, w_out, state_idx,
+//   next_idx, actions, rewards, dones, gammas, a_out, r_out, d_out, g_out, st_slots, nx_slots, B]
+//   (+ [cursor, n new transitions, capacity]: fused acting's PER insertion);
+// per_f: [alpha, eps, beta0, beta_steps]
+void opk_per(OptimPackArgs& a, PerStep& per, const std::vector<int64_t>& per_p, const std::vector<double>& per_f) {
+  if (per_p.empty()) return;
+  TORCH_CHECK(a.op >= 0 && a.smp == nullptr && (per_p.size() == 25 || per_p.size() == 28) && per_f.size() == 4,
+              "optim_pack per: 25 (+3 insertion) ints + 4 floats (update calls only, not with a uniform sample)");
+  for (int i : {0, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23})
+    TORCH_CHECK(per_p[i] != 0, "optim_pack per: null pointer ", i);
+  per.sum = P<float*>(per_p[0]); per.mn = P<float*>(per_p[1]); per.maxp = P<float*>(per_p[2]);
+  per.P = (int)per_p[3]; per.levels = (int)per_p[4];
+  per.upd_idx = P<const int32_t*>(per_p[5]); per.upd_td = P<const float*>(per_p[6]);
+  per.rng = P<int64_t*>(per_p[7]); per.size = P<const int32_t*>(per_p[8]); per.step = P<const int64_t*>(per_p[9]);
+  per.idx_out = P<int32_t*>(per_p[10]); per.w_out = P<float*>(per_p[11]);
+  per.so = SampleOut{P<const int32_t*>(per_p[12]), P<const int32_t*>(per_p[13]), 4, P<const int32_t*>(per_p[14]),
+                     P<const float*>(per_p[15]), P<const float*>(per_p[16]), P<const float*>(per_p[17]),
+                     P<int32_t*>(per_p[18]), P<float*>(per_p[19]), P<float*>(per_p[20]), P<float*>(per_p[21]),
+                     P<int32_t*>(per_p[22]), P<int32_t*>(per_p[23])};
+  per.B = (int)per_p[24];
+  if (per_p.size() == 28) {
+    per.ins_cursor = P<const int64_t*>(per_p[25]);
+    per.ins_n = (int)per_p[26];
+    per.ins_cap = (int)per_p[27];
+    TORCH_CHECK(per.ins_cursor != nullptr && per.ins_n >= 0 && per.ins_cap >= 1 && per.ins_n <= per.ins_cap &&
+                    per.ins_cap <= per.P, "optim_pack per: bad insertion spec");
+  }
+  per.alpha = (float)per_f[0]; per.eps = (float)per_f[1]; per.beta0 = (float)per_f[2];
+  per.beta_steps = (float)per_f[3];
+  TORCH_CHECK(per.B >= 1 && per.B <= 64 && per.P >= 2 && (per.P & (per.P - 1)) == 0 &&
+              (1 << per.levels) == per.P && per.levels <= 30 && per.beta_steps >= 1.f,
+              "optim_pack per: 1 <= B <= 64 (one-wave tree update), P = 2^levels, beta_steps >= 1");
+  TORCH_CHECK(per.B + per.ins_n <= 64, "optim_pack per: batch + inserted transitions <= 64 (one wave)");
+  a.per = &per;
+}
+
+// fc: [] or [x ptr, dh ptr, M, ldx, ldh] (act_t rows, optim.hip FcFuse)
+void opk_fc(OptimPackArgs& a, FcFuse& ff, const std::vector<int64_t>& fc) {
+  if (fc.empty()) return;
+  TORCH_CHECK(a.op >= 0 && fc.size() == 5 && fc[0] != 0 && fc[1] != 0 && fc[2] >= 1 && fc[2] <= 4096 &&
+                  fc[3] % 8 == 0 && fc[4] % 8 == 0 && (fc[0] % 16) == 0 && (fc[1] % 16) == 0,
+              "optim_pack fc: [x, dh, 1 <= M <= 4096, ldx % 8 == 0, ldh % 8 == 0], 16-byte aligned rows");
+  TORCH_CHECK(optim_fc_fuse(), "optim_pack fc: not available in this build");
+  ff = FcFuse{P<const void*>(fc[0]), P<const void*>(fc[1]), (int)fc[2], (int)fc[3], (int)fc[4]};
+  a.fc = &ff;
+}
+
+// (after opk_fc; a.part is set)
+void opk_wg(OptimPackArgs& a, int64_t wg, int64_t wg_blocks) {
+  if (wg != 0) {
+    TORCH_CHECK(wg_blocks >= 1 && wg_blocks <= 16384 && a.fc != nullptr && a.op >= 0 && a.part == nullptr &&
+                    (wg % 16) == 0, "optim_pack wg: needs fc rows and an update, no partials");
+  }
+  a.wg = P<const void*>(wg);
+  a.wg_blocks = (int)wg_blocks;
+}
+
+// dp: [] or [device DpExchange (xgmi_dpx_args), first, n, blocks]: the job table's dependent jobs
+// [first, first + n) run in `blocks` blocks (after opk_wg)
+void opk_dp(OptimPackArgs& a, dqn::DpLaunch& dpl, const std::vector<int64_t>& dp) {
+  if (dp.empty()) return;
+  TORCH_CHECK(a.wg != nullptr && dp.size() == 4 && dp[0] != 0 && (dp[0] % 16) == 0 && dp[2] >= 1 &&
+                  dp[2] <= dqn::kDpxMaxSlots && dp[1] >= 0 && dp[1] + dp[2] <= a.njobs && dp[3] >= 1 && dp[3] <= dp[2],
+              "optim_pack dp: [device DpExchange, first, n, blocks] with a WG launch, the dependent jobs inside "
+              "the table, 1 <= blocks <= n <= DPX_MAX_SLOTS");
+  dpl = dqn::DpLaunch{P<const dqn::DpExchange*>(dp[0]), (int)dp[1], (int)dp[2], (int)dp[3]};
+  a.dp = &dpl;
+}
+
 void optim_pack(int64_t op, torch::Tensor w, torch::Tensor grad, torch::Tensor s0, torch::Tensor s1,
                 torch::Tensor beta_pow, torch::Tensor ticket, double lr, double reg, int64_t reg_end,
                 double grad_scale, torch::Tensor step, std::vector<double> hp, torch::Tensor jobs,
-                torch::Tensor packed, c10::optional<torch::Tensor> target, c10::optional<torch::Tensor> target_packed,
-                int64_t target_freq, int64_t max_grid, c10::optional<torch::Tensor> noise,
-                c10::optional<torch::Tensor> eff, c10::optional<torch::Tensor> grad_noise,
-                c10::optional<torch::Tensor> noise_dst, std::vector<int64_t> sample, std::vector<int64_t> per_p,
-                std::vector<double> per_f, c10::optional<torch::Tensor> tnoise, c10::optional<torch::Tensor> teff,
-                c10::optional<torch::Tensor> tpk, c10::optional<torch::Tensor> noise_rng, std::vector<int64_t> fc,
-                int64_t part, int64_t wg, int64_t wg_blocks, std::vector<int64_t> dp, int64_t tsg, bool no_pack) {
-  // wg / wg_blocks: the launch also computes the grouped weight gradients -- a device WgradGroup
-  // (qnet_wgrad_plan) whose wg_blocks tiles follow the lead block; jobs with dep >= 0 wait for
-  // their member (needs fc: the launch forms the fc gradients from FcFuse rows)
-  // dp: [] or [device DpExchange (xgmi_dpx_args), first, n, blocks] (WG launches under data
-  //   parallelism): the job table's dependent jobs [first, first + n) sum their gradient over every
-  //   rank inside the launch, run by `blocks` blocks
-  // part: 0 or the base of the grouped conv wgrad's partial buffer (jobs with part_n > 0 sum it)
-  // fc: [] or [x ptr, dh ptr, M, ldx, ldh]: the launch forms the fc weight / bias gradient of the
-  // jobs carrying a dH column from those act_t rows (optim.hip FcFuse) instead of reading `grad`
-  // noise_rng (noisy nets): [seed, counter] of the noise stream whose next samples an earlier
-  // launch of this step drew (the fc dgrad's noise duty); the last block advances the counter
-  // tnoise / teff / tpk (noisy nets): mix + pack the target under tnoise in the same launch
-  // per_p: [] or [sum, min, max_p, P, levels, upd_idx, upd_td, rng, size, step, idx_out, w_out,
-  //   state_idx, next_idx, actions, rewards, dones, gammas, a_out, r_out, d_out, g_out, st_slots,
-  //   nx_slots, B] ; per_f: [alpha, eps, beta0, beta_steps] — prioritized variant of `sample`
-  // sample: [] or 16 pointers (TrunkSample order) + B: an extra block draws the next step's
-  // uniform minibatch (frame-stacked replay, k = 4)
-  // grad_noise: derive the sigma gradients from the mu gradients under that noise sample;
-  // noise_dst: the last block copies `noise` there (next sample becomes the current one)
-  // op -1: no optimizer update, only the (noisy) mix + pack of w (noise / eff given)
-  // tsg: 0 or the sigma-fragment buffer (packed layout) of a factorised target (UpdJob.eff bit 1):
-  //   update calls with tnoise write it at a sync step, mix-only calls on that target every time
-  // no_pack: update only (no packed fragments / copies; the async-PS server)
+                torch::Tensor packed, OptTensor target, OptTensor target_packed, int64_t target_freq,
+                int64_t max_grid, OptTensor noise, OptTensor eff, OptTensor grad_noise, OptTensor noise_dst,
+                std::vector<int64_t> sample, std::vector<int64_t> per_p, std::vector<double> per_f, OptTensor tnoise,
+                OptTensor teff, OptTensor tpk, OptTensor noise_rng, std::vector<int64_t> fc, int64_t part, int64_t wg,
+                int64_t wg_blocks, std::vector<int64_t> dp, int64_t tsg, bool no_pack) {
   CHECK_T(w, torch::kFloat32); CHECK_T(grad, torch::kFloat32); CHECK_T(s0, torch::kFloat32);
   CHECK_T(s1, torch::kFloat32); CHECK_T(beta_pow, torch::kFloat32); CHECK_T(ticket, torch::kInt32);
-  CHECK_T(step, torch::kInt64); CHECK_T(jobs, torch::kInt32); CHECK_T(packed, DQN_ACT_F32 ? torch::kFloat32 : DQN_ACT_F16 ? torch::kHalf : torch::kBFloat16);
+  CHECK_T(step, torch::kInt64); CHECK_T(jobs, torch::kInt32); CHECK_T(packed, kActDtype);
   TORCH_CHECK(grad.numel() == w.numel() && hp.size() == 9, "optim_pack args");
   TORCH_CHECK(jobs.numel() % upd_job_ints() == 0, "optim_pack: job table size");
   TORCH_CHECK(ticket.numel() >= 17 * 32, "optim_pack: the end-of-launch arrival counters need the 17x32-word ticket");
   TORCH_CHECK(max_grid >= 1 && max_grid <= 65535, "optim_pack: max_grid");
   TORCH_CHECK(op >= -1 && op <= 7, "optim_pack: op (7 = rmsprop without momentum)");
-  float* tgt = nullptr;
-  void* tgtp = nullptr;
-  if (target.has_value() && target->defined()) {
-    CHECK_T((*target), torch::kFloat32);
-    TORCH_CHECK(target->numel() == w.numel() && target_freq >= 1, "optim_pack: target sync args");
-    tgt = ptr<float>(*target);
-    if (target_packed.has_value() && target_packed->defined()) {   // noisy nets: fp32 target only
-      TORCH_CHECK(target_packed->numel() == packed.numel(), "optim_pack: target packed size");
-      tgtp = target_packed->data_ptr();
-    }
-  }
-  const float* nz = nullptr;
-  float* ef = nullptr;
-  if (noise.has_value() && noise->defined()) {
-    CHECK_T((*noise), torch::kFloat32);
-    nz = ptr<float>(*noise);
-  }
-  if (eff.has_value() && eff->defined()) {
-    CHECK_T((*eff), torch::kFloat32);
-    TORCH_CHECK(eff->numel() == w.numel(), "optim_pack: eff size");
-    ef = ptr<float>(*eff);
-  }
-  TORCH_CHECK(op >= 0 || tgt == nullptr, "optim_pack: mix-only call with a target");
-  const float* gnz = nullptr;
-  float* ndst = nullptr;
-  int nn = 0;
-  if (grad_noise.has_value() && grad_noise->defined()) {
-    CHECK_T((*grad_noise), torch::kFloat32);
-    TORCH_CHECK(nz != nullptr && grad_noise->numel() == noise->numel(), "optim_pack: grad_noise size");
-    gnz = ptr<float>(*grad_noise);
-  }
-  if (noise_dst.has_value() && noise_dst->defined()) {
-    CHECK_T((*noise_dst), torch::kFloat32);
-    TORCH_CHECK(op >= 0 && nz != nullptr && noise_dst->numel() == noise->numel() &&
-                noise_dst->data_ptr() != noise->data_ptr(), "optim_pack: noise_dst");
-    ndst = ptr<float>(*noise_dst);
-    nn = (int)noise_dst->numel();
-  }
-  dqn::TrunkSample smp{};
-  if (!sample.empty()) {
-    TORCH_CHECK(op >= 0 && sample.size() == 17, "optim_pack sample: 16 pointers + B (update calls only)");
-    for (int i = 0; i < 16; ++i) TORCH_CHECK(sample[i] != 0, "optim_pack sample: null pointer");
-    smp.size = P<const int32_t*>(sample[0]); smp.rng = P<int64_t*>(sample[1]); smp.ticket = P<int32_t*>(sample[2]);
-    smp.state_idx = P<const int32_t*>(sample[3]); smp.next_idx = P<const int32_t*>(sample[4]);
-    smp.actions = P<const int32_t*>(sample[5]); smp.rewards = P<const float*>(sample[6]);
-    smp.dones = P<const float*>(sample[7]); smp.gammas = P<const float*>(sample[8]);
-    smp.idx_out = P<int32_t*>(sample[9]); smp.a_out = P<int32_t*>(sample[10]); smp.r_out = P<float*>(sample[11]);
-    smp.d_out = P<float*>(sample[12]); smp.g_out = P<float*>(sample[13]);
-    smp.st_slots = P<int32_t*>(sample[14]); smp.nx_slots = P<int32_t*>(sample[15]);
-    smp.B = (int)sample[16];
-    smp.ninst = 0;
-    TORCH_CHECK(smp.B >= 1 && smp.B <= 512, "optim_pack sample: 1 <= B <= 512 (one lane per sample)");
-  }
-  PerStep per{};
-  if (!per_p.empty()) {
-    TORCH_CHECK(op >= 0 && sample.empty() && (per_p.size() == 25 || per_p.size() == 28) && per_f.size() == 4,
-                "optim_pack per: 25 (+3 insertion) ints + 4 floats (update calls only, not with a uniform sample)");
-    for (int i : {0, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23})
-      TORCH_CHECK(per_p[i] != 0, "optim_pack per: null pointer ", i);
-    per.sum = P<float*>(per_p[0]); per.mn = P<float*>(per_p[1]); per.maxp = P<float*>(per_p[2]);
-    per.P = (int)per_p[3]; per.levels = (int)per_p[4];
-    per.upd_idx = P<const int32_t*>(per_p[5]); per.upd_td = P<const float*>(per_p[6]);
-    per.rng = P<int64_t*>(per_p[7]); per.size = P<const int32_t*>(per_p[8]); per.step = P<const int64_t*>(per_p[9]);
-    per.idx_out = P<int32_t*>(per_p[10]); per.w_out = P<float*>(per_p[11]);
-    per.so = SampleOut{P<const int32_t*>(per_p[12]), P<const int32_t*>(per_p[13]), 4, P<const int32_t*>(per_p[14]),
-                       P<const float*>(per_p[15]), P<const float*>(per_p[16]), P<const float*>(per_p[17]),
-                       P<int32_t*>(per_p[18]), P<float*>(per_p[19]), P<float*>(per_p[20]), P<float*>(per_p[21]),
-                       P<int32_t*>(per_p[22]), P<int32_t*>(per_p[23])};
-    per.B = (int)per_p[24];
-    if (per_p.size() == 28) {        // [cursor, n new transitions, capacity]: fused acting's PER insertion
-      per.ins_cursor = P<const int64_t*>(per_p[25]);
-      per.ins_n = (int)per_p[26];
-      per.ins_cap = (int)per_p[27];
-      TORCH_CHECK(per.ins_cursor != nullptr && per.ins_n >= 0 && per.ins_cap >= 1 && per.ins_n <= per.ins_cap &&
-                      per.ins_cap <= per.P, "optim_pack per: bad insertion spec");
-    }
-    per.alpha = (float)per_f[0]; per.eps = (float)per_f[1]; per.beta0 = (float)per_f[2];
-    per.beta_steps = (float)per_f[3];
-    TORCH_CHECK(per.B >= 1 && per.B <= 64 && per.P >= 2 && (per.P & (per.P - 1)) == 0 &&
-                (1 << per.levels) == per.P && per.levels <= 30 && per.beta_steps >= 1.f,
-                "optim_pack per: 1 <= B <= 64 (one-wave tree update), P = 2^levels, beta_steps >= 1");
-    TORCH_CHECK(per.B + per.ins_n <= 64, "optim_pack per: batch + inserted transitions <= 64 (one wave)");
-  }
-  const float* tnz = nullptr;
-  float* tef = nullptr;
-  void* tpkp = nullptr;
-  if (tnoise.has_value() && tnoise->defined()) {
-    CHECK_T((*tnoise), torch::kFloat32);
-    TORCH_CHECK(op >= 0 && tgt != nullptr && nz != nullptr && tnoise->numel() == noise->numel() &&
-                teff.has_value() && teff->defined() && tpk.has_value() && tpk->defined(),
-                "optim_pack: target mix needs target, noise, teff, tpk");
-    CHECK_T((*teff), torch::kFloat32);
-    CHECK_T((*tpk), DQN_ACT_F32 ? torch::kFloat32 : DQN_ACT_F16 ? torch::kHalf : torch::kBFloat16);
-    TORCH_CHECK(teff->numel() == w.numel() && tpk->numel() == packed.numel() && tpk->data_ptr() != packed.data_ptr(),
-                "optim_pack: teff / tpk sizes");
-    tnz = ptr<float>(*tnoise);
-    tef = ptr<float>(*teff);
-    tpkp = tpk->data_ptr();
-  }
-  int64_t* nrng = nullptr;
-  if (noise_rng.has_value() && noise_rng->defined()) {
-    CHECK_T((*noise_rng), torch::kInt64);
-    TORCH_CHECK(op >= 0 && noise_rng->numel() >= 2, "optim_pack: noise_rng = [seed, counter] (update calls)");
-    nrng = ptr<int64_t>(*noise_rng);
-  }
-  FcFuse ff{nullptr, nullptr, 0, 0, 0};
-  if (!fc.empty()) {
-    TORCH_CHECK(op >= 0 && fc.size() == 5 && fc[0] != 0 && fc[1] != 0 && fc[2] >= 1 && fc[2] <= 4096 &&
-                    fc[3] % 8 == 0 && fc[4] % 8 == 0 && (fc[0] % 16) == 0 && (fc[1] % 16) == 0,
-                "optim_pack fc: [x, dh, 1 <= M <= 4096, ldx % 8 == 0, ldh % 8 == 0], 16-byte aligned rows");
-    TORCH_CHECK(optim_fc_fuse(), "optim_pack fc: not available in this build");
-    TORCH_CHECK(ticket.numel() >= 17 * 32, "optim_pack fc: one block per job needs the 17x32-word ticket");
-    ff = FcFuse{P<const void*>(fc[0]), P<const void*>(fc[1]), (int)fc[2], (int)fc[3], (int)fc[4]};
-  }
-  TORCH_CHECK(ticket.numel() >= 2, "optim_pack: ticket[1] is the slot flag word");
-  if (wg != 0) {
-    TORCH_CHECK(wg_blocks >= 1 && wg_blocks <= 16384 && !fc.empty() && op >= 0 && part == 0 && (wg % 16) == 0,
-                "optim_pack wg: needs fc rows and an update, no partials");
-  }
-  dqn::DpLaunch dpl{nullptr, 0, 0, 0};
-  if (!dp.empty()) {
-    const int64_t nj = jobs.numel() / upd_job_ints();
-    TORCH_CHECK(wg != 0 && dp.size() == 4 && dp[0] != 0 && (dp[0] % 16) == 0 && dp[2] >= 1 &&
-                    dp[2] <= dqn::kDpxMaxSlots && dp[1] >= 0 && dp[1] + dp[2] <= nj && dp[3] >= 1 && dp[3] <= dp[2],
-                "optim_pack dp: [device DpExchange, first, n, blocks] with a WG launch, the dependent jobs inside "
-                "the table, 1 <= blocks <= n <= DPX_MAX_SLOTS");
-    dpl = dqn::DpLaunch{P<const dqn::DpExchange*>(dp[0]), (int)dp[1], (int)dp[2], (int)dp[3]};
-  }
   float h[9];
   for (int i = 0; i < 9; ++i) h[i] = (float)hp[i];
+  OptimPackArgs a{};
+  a.op = (int)op; a.w = ptr<float>(w); a.g = ptr<float>(grad); a.s0 = ptr<float>(s0); a.s1 = ptr<float>(s1);
+  a.beta_pow = ptr<float>(beta_pow); a.step = ptr<int64_t>(step); a.ticket = ptr<int32_t>(ticket); a.hp9 = h;
+  a.lr = (float)lr; a.reg = (float)reg; a.reg_end = (int)reg_end; a.grad_scale = (float)grad_scale;
+  a.jobs = jobs.data_ptr(); a.njobs = (int)(jobs.numel() / upd_job_ints()); a.packed = packed.data_ptr();
+  a.max_grid = (int)max_grid; a.no_pack = no_pack ? 1 : 0; a.part = P<const float*>(part);
+  dqn::TrunkSample smp{};
+  PerStep per{};
+  FcFuse ff{};
+  dqn::DpLaunch dpl{};
+  opk_target(a, target, target_packed, target_freq, tsg, w, packed);
+  opk_noise(a, noise, eff, grad_noise, noise_dst, noise_rng, tnoise, teff, tpk, w, packed);
+  opk_sample(a, smp, sample);
+  opk_per(a, per, per_p, per_f);
+  opk_fc(a, ff, fc);
+  opk_wg(a, wg, wg_blocks);
+  opk_dp(a, dpl, dp);
   c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
-  const bool launched =
-      launch_optim_pack((int)op, ptr<float>(w), ptr<float>(grad), ptr<float>(s0), ptr<float>(s1), ptr<float>(beta_pow),
-                    ptr<int64_t>(step), ptr<int32_t>(ticket), h, (float)lr, (float)reg, (int)reg_end,
-                    (float)grad_scale, jobs.data_ptr(), (int)(jobs.numel() / upd_job_ints()), packed.data_ptr(), tgt,
-                    tgtp, (int)target_freq, (int)max_grid, nz, ef, gnz, ndst, nn, sample.empty() ? nullptr : &smp,
-                    per_p.empty() ? nullptr : &per, tnz, tef, tpkp, nrng, fc.empty() ? nullptr : &ff,
-                    reinterpret_cast<const float*>(part), reinterpret_cast<const void*>(wg), (int)wg_blocks,
-                    dp.empty() ? nullptr : &dpl, reinterpret_cast<void*>(tsg), no_pack ? 1 : 0, cur_stream());
-  TORCH_CHECK(launched, "optim_pack: the launcher refused these arguments and launched nothing: no kernel is built "
+  TORCH_CHECK(launch_optim_pack(a, cur_stream()),
+              "optim_pack: the launcher refused these arguments and launched nothing: no kernel is built "
               "for optimizer ", op, " with this combination of noise, target_noise, per, fc, wg and dp, or a wg / dp "
               "argument failed the launcher's own check");
 }
@@ -636,13 +632,13 @@ void xgmi_allreduce(torch::Tensor grad, std::vector<int64_t> data, std::vector<i
 
 // srcs / outs: two segments each (byte pointers); bytes: per-rank segment sizes; cap: staging
 // bytes per parity of this channel
-void xgmi_allgather(std::vector<int64_t> srcs, std::vector<int64_t> outs, std::vector<int64_t> bytes,
-                    std::vector<int64_t> data, std::vector<int64_t> sig, int64_t seq, int64_t err, int64_t cap,
-                    int64_t rank, int64_t world, int64_t blocks, int64_t device) {
+dqn::XgmiGatherArgs gather_args(const std::vector<int64_t>& srcs, const std::vector<int64_t>& outs,
+                                const std::vector<int64_t>& bytes, const std::vector<int64_t>& data,
+                                const std::vector<int64_t>& sig, int64_t seq, int64_t err, int64_t cap, int64_t rank,
+                                int64_t world) {
   TORCH_CHECK(world >= 1 && world <= dqn::kXgmiMaxRanks && rank >= 0 && rank < world, "xgmi gather: rank/world");
   TORCH_CHECK((int64_t)data.size() == world && (int64_t)sig.size() == world && seq && err, "xgmi gather: pointers");
   TORCH_CHECK(srcs.size() == 2 && outs.size() == 2 && bytes.size() == 2, "xgmi gather: two segments");
-  TORCH_CHECK(blocks >= 1 && blocks <= dqn::kXgmiMaxBlocks, "xgmi gather: blocks");
   dqn::XgmiGatherArgs g{};
   for (int i = 0; i < world; ++i) {
     TORCH_CHECK(data[i] && sig[i], "xgmi gather: null peer pointer");
@@ -661,6 +657,14 @@ void xgmi_allgather(std::vector<int64_t> srcs, std::vector<int64_t> outs, std::v
   g.x.err = reinterpret_cast<int*>(err);
   g.x.cap = cap;
   g.x.rank = (int)rank; g.x.world = (int)world;
+  return g;
+}
+
+void xgmi_allgather(std::vector<int64_t> srcs, std::vector<int64_t> outs, std::vector<int64_t> bytes,
+                    std::vector<int64_t> data, std::vector<int64_t> sig, int64_t seq, int64_t err, int64_t cap,
+                    int64_t rank, int64_t world, int64_t blocks, int64_t device) {
+  TORCH_CHECK(blocks >= 1 && blocks <= dqn::kXgmiMaxBlocks, "xgmi gather: blocks");
+  const dqn::XgmiGatherArgs g = gather_args(srcs, outs, bytes, data, sig, seq, err, cap, rank, world);
   c10::hip::HIPGuardMasqueradingAsCUDA guard((c10::DeviceIndex)device);
   TORCH_CHECK(launch_xgmi_allgather(g, (int)blocks, cur_stream()) == 0, "xgmi gather: launch arguments");
 }
@@ -670,27 +674,7 @@ void xgmi_allgather(std::vector<int64_t> srcs, std::vector<int64_t> outs, std::v
 torch::Tensor xgmi_gather_args(std::vector<int64_t> srcs, std::vector<int64_t> outs, std::vector<int64_t> bytes,
                                std::vector<int64_t> data, std::vector<int64_t> sig, int64_t seq, int64_t err,
                                int64_t cap, int64_t rank, int64_t world) {
-  TORCH_CHECK(world >= 1 && world <= dqn::kXgmiMaxRanks && rank >= 0 && rank < world, "xgmi gather: rank/world");
-  TORCH_CHECK((int64_t)data.size() == world && (int64_t)sig.size() == world && seq && err, "xgmi gather: pointers");
-  TORCH_CHECK(srcs.size() == 2 && outs.size() == 2 && bytes.size() == 2, "xgmi gather: two segments");
-  dqn::XgmiGatherArgs g{};
-  for (int i = 0; i < world; ++i) {
-    TORCH_CHECK(data[i] && sig[i], "xgmi gather: null peer pointer");
-    g.x.data[i] = reinterpret_cast<void*>(data[i]);
-    g.x.sig[i] = reinterpret_cast<uint32_t*>(sig[i]);
-  }
-  for (int q = 0; q < 2; ++q) {
-    TORCH_CHECK(srcs[q] && outs[q] && bytes[q] >= 0 && bytes[q] % 16 == 0 && (srcs[q] & 15) == 0 && (outs[q] & 15) == 0,
-                "xgmi gather: 16-byte aligned segments, sizes % 16 == 0");
-    g.src[q] = reinterpret_cast<const void*>(srcs[q]);
-    g.out[q] = reinterpret_cast<void*>(outs[q]);
-    g.bytes[q] = bytes[q];
-  }
-  TORCH_CHECK(bytes[0] + bytes[1] <= cap, "xgmi gather: payload exceeds the channel's staging");
-  g.x.seq = reinterpret_cast<uint32_t*>(seq);
-  g.x.err = reinterpret_cast<int*>(err);
-  g.x.cap = cap;
-  g.x.rank = (int)rank; g.x.world = (int)world;
+  const dqn::XgmiGatherArgs g = gather_args(srcs, outs, bytes, data, sig, seq, err, cap, rank, world);
   auto out = torch::empty({(int64_t)sizeof(g)}, torch::kUInt8);
   std::memcpy(out.data_ptr(), &g, sizeof(g));
   return out;
@@ -776,6 +760,8 @@ void register_ps_server(pybind11::module_& m);      // ps_server.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "dist_dqn_amd native extension (gfx950 HIP kernels + C++ host runtime)";
+  const pybind11::none none;
+  const std::vector<int64_t> no_ints;
   m.def("replay_sample_uniform", &replay_sample_uniform);
   m.def("mlp", &mlp);
   m.def("mlp_lds_bytes", &mlp_lds_bytes);
@@ -817,12 +803,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("s0"), pybind11::arg("s1"), pybind11::arg("beta_pow"), pybind11::arg("ticket"),
         pybind11::arg("lr"), pybind11::arg("reg"), pybind11::arg("reg_end"), pybind11::arg("grad_scale"),
         pybind11::arg("step"), pybind11::arg("hp"), pybind11::arg("jobs"), pybind11::arg("packed"),
-        pybind11::arg("target"), pybind11::arg("target_packed"), pybind11::arg("target_freq"),
-        pybind11::arg("max_grid"), pybind11::arg("noise"), pybind11::arg("eff"), pybind11::arg("grad_noise"),
-        pybind11::arg("noise_dst"), pybind11::arg("sample"), pybind11::arg("per_p"), pybind11::arg("per_f"),
-        pybind11::arg("tnoise"), pybind11::arg("teff"), pybind11::arg("tpk"), pybind11::arg("noise_rng"),
-        pybind11::arg("fc"), pybind11::arg("part"), pybind11::arg("wg") = 0, pybind11::arg("wg_blocks") = 0,
-        pybind11::arg("dp") = std::vector<int64_t>{}, pybind11::arg("tsg") = 0, pybind11::arg("no_pack") = false);
+        pybind11::arg("target") = none, pybind11::arg("target_packed") = none, pybind11::arg("target_freq") = 1,
+        pybind11::arg("max_grid"), pybind11::arg("noise") = none, pybind11::arg("eff") = none,
+        pybind11::arg("grad_noise") = none, pybind11::arg("noise_dst") = none, pybind11::arg("sample") = no_ints,
+        pybind11::arg("per_p") = no_ints, pybind11::arg("per_f") = std::vector<double>{},
+        pybind11::arg("tnoise") = none, pybind11::arg("teff") = none, pybind11::arg("tpk") = none,
+        pybind11::arg("noise_rng") = none, pybind11::arg("fc") = no_ints, pybind11::arg("part") = 0,
+        pybind11::arg("wg") = 0, pybind11::arg("wg_blocks") = 0, pybind11::arg("dp") = no_ints,
+        pybind11::arg("tsg") = 0, pybind11::arg("no_pack") = false);
+  m.attr("OPTIM_PACK_ARGS_BYTES") = (int)sizeof(OptimPackArgs);   // (tests mirror the struct with ctypes)
   m.def("noise_normal", &noise_normal);
   m.attr("UPD_JOB_INTS") = upd_job_ints();
   m.def("optim_prof", []() {

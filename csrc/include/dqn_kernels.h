@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace dqn { struct TrunkSample; }   // dqn_nets_k.h
+namespace dqn { struct TrunkSample; struct DpLaunch; }   // dqn_nets_k.h; below
 
 // Optional outputs of the sampling kernels: per-sample scalars and the frame-slot
 // tables of s and s' (so conv1 can read the frame ring directly). st_slots == nullptr: skip.
@@ -53,17 +53,54 @@ struct FcFuse {
   const void* dh;
   int M, ldx, ldh;
 };
-// dp: nullptr or a dqn::DpLaunch (WG launches under data parallelism: the dependent jobs exchange
-// their gradients with every rank inside the launch, see DpExchange below).
+// Everything one optimizer step fused with the executor's weight packing takes (optim.hip
+// optim_pack_kernel) but the stream. Scalars and pointers only, null / 0 = absent: the binding fills
+// it group by group, and tests/test_ext_variants.py mirrors it field by field (OPTIM_PACK_ARGS_BYTES).
+struct OptimPackArgs {
+  // ---- core buffers and hyper-parameters
+  int op;                    // optimizer (optim.py kernel_op; 7 = rmsprop without momentum); -1: no
+                             // update, only the (noisy) mix + pack of w (noise / eff given)
+  float* w; const float* g;  // flat fp32 parameters and their gradient
+  float* s0; float* s1;      // optimizer slots (w itself where the optimizer has none)
+  float* beta_pow;           // [2] Adam's beta powers, advanced by the launch
+  int64_t* step;             // device global_step, advanced by the launch
+  int32_t* ticket;           // 17 x 32 words: arrival counters, [1] the slot flag word, [2] the error word
+  const float* hp9;          // host: momentum, rho, rms_mom, rms_eps, b1, b2, adam_eps, ad_rho, ad_eps
+  float lr, reg;
+  int reg_end;               // w[:reg_end] carries the L2 term
+  float grad_scale;          // (1 / world under data parallelism)
+  // ---- job table and packed output
+  const void* jobs; int njobs;   // device UpdJob rows (optim_pack.h)
+  void* packed;              // act_t fragments of w, rewritten by the launch
+  int max_grid;              // job blocks of the launch (grid-stride beyond it)
+  int no_pack;               // 1: update only, no packed fragments / copies (the async-PS server)
+  const float* part;         // base of the grouped conv wgrad's partial buffer (jobs with part_n > 0 sum it)
+  // ---- target: hard sync every tfreq steps, under the device step
+  float* tgt; void* tgt_packed;  // (tgt_packed: plain nets only; a noisy target is re-mixed, see tpk)
+  int tfreq;
+  void* tsg;                 // sigma-fragment buffer (packed layout) of a factorised target (UpdJob.eff bit 1):
+                             // update calls with tnoise write it at a sync step, mix-only calls on that target every time
+  // ---- noise (noisy nets)
+  const float* noise; float* eff;   // the sample mixed into packed, and the fp32 effective values
+  const float* gnoise;       // derive the sigma gradients from the mu gradients under this sample
+  float* noise_dst; int noise_n;    // the last block copies noise[:noise_n] there (next sample becomes the current one)
+  int64_t* noise_rng;        // [seed, counter] of the noise stream whose next samples an earlier launch of
+                             // this step drew (the fc dgrad's noise duty); the last block advances the counter
+  const float* tnoise; float* teff; void* tpk;   // mix + pack the target under tnoise in the same launch
+  // ---- sampler: an extra block draws the next step's minibatch (frame-stacked replay, k = 4)
+  const dqn::TrunkSample* smp;   // uniform
+  const PerStep* per;        // prioritized, after writing this step's priorities
+  // ---- fused gradients
+  const FcFuse* fc;          // the jobs carrying a dH column form their gradient from these rows, not from g
+  const void* wg; int wg_blocks;   // device WgradGroup (qnet_wgrad_plan): the launch also computes the grouped weight
+                             // gradients, its wg_blocks tiles follow the lead block; jobs with dep >= 0 wait for
+                             // their member (needs fc)
+  const dqn::DpLaunch* dp;   // WG launches under data parallelism: the dependent jobs exchange their
+                             // gradients with every rank inside the launch (DpExchange below)
+};
 // Returns false, with nothing enqueued, when the arguments select a launch this build does not
 // instantiate (optim_pack.h DQN_OPT_MODES) or fail the binding's own checks.
-bool launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
-                       int32_t* ticket, const float* hp9, float lr, float reg, int reg_end, float grad_scale,
-                       const void* jobs, int njobs, void* packed, float* tgt, void* tgt_packed, int tfreq, int max_grid,
-                       const float* noise, float* eff, const float* gnoise, float* noise_dst, int noise_n,
-                       const dqn::TrunkSample* smp, const PerStep* per, const float* tnoise, float* teff, void* tpk,
-                       int64_t* noise_rng, const FcFuse* fc, const float* part, const void* wg, int wg_blocks,
-                       const void* dp, void* tsg, int no_pack, hipStream_t st);
+bool launch_optim_pack(const OptimPackArgs& a, hipStream_t st);
 // 1 when this build's optimizer launch can form the fc weight gradient itself (16-bit builds)
 int optim_fc_fuse();
 // probe launches (DQN_OPT_PROF=1): per-block [start, ready, end] s_memrealtime stamps of the last launch

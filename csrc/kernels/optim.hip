@@ -125,91 +125,75 @@ static int grid_for_ticket(int n4) {
   return g < 1 ? 1 : (g > 256 ? 256 : g);
 }
 
-void launch_optimizer_step(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow,
-                           int64_t* step, int32_t* ticket, const float* hp9, float lr, float reg, int reg_end,
-                           float grad_scale, int n, float* tgt, int tfreq, hipStream_t st) {
+// the scalars + hp9 = [momentum, rho, rms_mom, rms_eps, b1, b2, adam_eps, ad_rho, ad_eps]; prof / tsg /
+// no_pack stay zero
+static OptHP opt_hp(float lr, float reg, int reg_end, float grad_scale, const float* hp9) {
   OptHP h{};
   h.lr = lr; h.reg = reg; h.grad_scale = grad_scale; h.reg_end = reg_end;
   h.momentum = hp9[0]; h.rho = hp9[1]; h.rms_mom = hp9[2]; h.rms_eps = hp9[3];
   h.b1 = hp9[4]; h.b2 = hp9[5]; h.adam_eps = hp9[6]; h.ad_rho = hp9[7]; h.ad_eps = hp9[8];
-  h.prof = nullptr;
-  const int n4 = n / 4;
-  dim3 grid(grid_for_ticket(n4)), block(256);
-  switch (op) {
-    case 0: hipLaunchKernelGGL(optim_kernel<0>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 1: hipLaunchKernelGGL(optim_kernel<1>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 2: hipLaunchKernelGGL(optim_kernel<2>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 3: hipLaunchKernelGGL(optim_kernel<3>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 4: hipLaunchKernelGGL(optim_kernel<4>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 5: hipLaunchKernelGGL(optim_kernel<5>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 6: hipLaunchKernelGGL(optim_kernel<6>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    case 7: hipLaunchKernelGGL(optim_kernel<7>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, tfreq < 1 ? 1 : tfreq); break;
-    default: break;
-  }
+  return h;
 }
 
-bool launch_optim_pack(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow, int64_t* step,
-                       int32_t* ticket, const float* hp9, float lr, float reg, int reg_end, float grad_scale,
-                       const void* jobs, int njobs, void* packed, float* tgt, void* tgt_packed, int tfreq,
-                       int max_grid, const float* noise, float* eff, const float* gnoise, float* noise_dst,
-                       int noise_n, const TrunkSample* smp, const PerStep* per, const float* tnoise, float* teff,
-                       void* tpk, int64_t* noise_rng, const FcFuse* fc, const float* part, const void* wg,
-                       int wg_blocks, const void* dp, void* tsg, int no_pack, hipStream_t st) {
-  OptPackLaunch L{};
-  OptHP& h = L.h;
-  h.lr = lr; h.reg = reg; h.grad_scale = grad_scale; h.reg_end = reg_end;
-  h.momentum = hp9[0]; h.rho = hp9[1]; h.rms_mom = hp9[2]; h.rms_eps = hp9[3];
-  h.b1 = hp9[4]; h.b2 = hp9[5]; h.adam_eps = hp9[6]; h.ad_rho = hp9[7]; h.ad_eps = hp9[8];
-  h.prof = optim_prof_buffer();
-  h.tsg = tsg;
-  h.no_pack = no_pack;
+void launch_optimizer_step(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow,
+                           int64_t* step, int32_t* ticket, const float* hp9, float lr, float reg, int reg_end,
+                           float grad_scale, int n, float* tgt, int tfreq, hipStream_t st) {
+  const OptHP h = opt_hp(lr, reg, reg_end, grad_scale, hp9);
+  const int n4 = n / 4;
+  dim3 grid(grid_for_ticket(n4)), block(256);
+#define OPT_CASE(N) \
+  case N: hipLaunchKernelGGL(optim_kernel<N>, grid, block, 0, st, w, g, s0, s1, beta_pow, step, ticket, h, n4, tgt, \
+                             tfreq < 1 ? 1 : tfreq); break;
+  switch (op) {
+    OPT_CASE(0) OPT_CASE(1) OPT_CASE(2) OPT_CASE(3) OPT_CASE(4) OPT_CASE(5) OPT_CASE(6) OPT_CASE(7)
+    default: break;
+  }
+#undef OPT_CASE
+}
+
+bool launch_optim_pack(const OptimPackArgs& a, hipStream_t st) {
+  OptPackLaunch L{a};
+  L.h = opt_hp(a.lr, a.reg, a.reg_end, a.grad_scale, a.hp9);
+  L.h.prof = optim_prof_buffer();
+  L.h.tsg = a.tsg;
+  L.h.no_pack = a.no_pack;
   // one block per job up to max_grid (grid-stride beyond it); block 0 (+1 sampler block when the
   // launch draws the next minibatch) closes the launch once every other block has arrived
-  const FcFuse ff = (fc != nullptr && optim_fc_fuse()) ? *fc : FcFuse{nullptr, nullptr, 0, 0, 0};
+  L.ff = (a.fc != nullptr && optim_fc_fuse()) ? *a.fc : FcFuse{nullptr, nullptr, 0, 0, 0};
+  const bool fcm = L.ff.x != nullptr;
   // (the FC modes run exactly one job per block)
-  const int cap = ff.x != nullptr ? (njobs > 256 ? njobs : 256) : (max_grid > 256 ? max_grid : 256);
-  L.smp = smp != nullptr ? *smp : TrunkSample{};
-  L.per = per != nullptr ? *per : PerStep{};
+  const int cap = fcm ? (a.njobs > 256 ? a.njobs : 256) : (a.max_grid > 256 ? a.max_grid : 256);
+  L.smp = a.smp != nullptr ? *a.smp : TrunkSample{};
+  L.per = a.per != nullptr ? *a.per : PerStep{};
   // WG: the launch also computes the grouped weight gradients (tiles after the lead block)
-  const bool wgm = wg != nullptr && ff.x != nullptr && op >= 0;
-  if (wg != nullptr && !wgm) return false;   // (binding checks: a WG launch needs FcFuse rows and an update)
+  const bool wgm = a.wg != nullptr && fcm && a.op >= 0;
+  if (a.wg != nullptr && !wgm) return false;   // (binding checks: a WG launch needs FcFuse rows and an update)
   // DP (WG under data parallelism): the dependent jobs run in dp->blocks blocks
-  const DpLaunch dpl = (wgm && dp != nullptr) ? *reinterpret_cast<const DpLaunch*>(dp) : DpLaunch{nullptr, 0, 0, 0};
-  if (dp != nullptr && (dpl.x == nullptr || dpl.blocks < 1 || dpl.blocks > dpl.n || dpl.first < 0 ||
-                        dpl.first + dpl.n > njobs || dpl.n > kDpxMaxSlots))
+  L.dp = (wgm && a.dp != nullptr) ? *a.dp : DpLaunch{nullptr, 0, 0, 0};
+  const DpLaunch& dpl = L.dp;
+  if (a.dp != nullptr && (dpl.x == nullptr || dpl.blocks < 1 || dpl.blocks > dpl.n || dpl.first < 0 ||
+                          dpl.first + dpl.n > a.njobs || dpl.n > kDpxMaxSlots))
     return false;                         // (binding checks)
-  const int nblk_jobs = dpl.x != nullptr ? njobs - dpl.n + dpl.blocks : njobs;
+  const int nblk_jobs = dpl.x != nullptr ? a.njobs - dpl.n + dpl.blocks : a.njobs;
   // + the lead block (sampler / closer) + the weight-gradient tiles
+  L.wg_blocks = wgm ? a.wg_blocks : 0;
   L.grid = (nblk_jobs < cap ? nblk_jobs : cap) + (L.smp.size != nullptr || L.per.sum != nullptr || wgm ? 1 : 0) +
-           (wgm ? wg_blocks : 0);
+           L.wg_blocks;
   // (a noisy net always passes its noise sample; plain nets pass none)
-  L.mode = (noise != nullptr ? kModeNoisy : 0) | (tnoise != nullptr ? kModeTmix : 0) |
-           (L.per.sum != nullptr ? kModePer : 0) | (ff.x != nullptr && op >= 0 ? kModeFc : 0) | (wgm ? kModeWg : 0) |
+  L.mode = (a.noise != nullptr ? kModeNoisy : 0) | (a.tnoise != nullptr ? kModeTmix : 0) |
+           (L.per.sum != nullptr ? kModePer : 0) | (fcm && a.op >= 0 ? kModeFc : 0) | (wgm ? kModeWg : 0) |
            (dpl.x != nullptr ? kModeDp : 0);
   // few work blocks (16-bit builds, the common optimizers): no spills, returning-ticket close
-  L.few = !DQN_ACT_F32 && !wgm && ff.x == nullptr && njobs <= 256 && (op == 0 || op == 3 || op == 7);
+  L.few = !DQN_ACT_F32 && !wgm && !fcm && a.njobs <= 256 && (a.op == 0 || a.op == 3 || a.op == 7);
   L.dyn = wgm ? (size_t)kFusedWgLds : 0;
   L.st = st;
-  L.w = w; L.g = g; L.s0 = s0; L.s1 = s1; L.beta_pow = beta_pow; L.step = step; L.ticket = ticket;
-  L.jobs = reinterpret_cast<const UpdJob*>(jobs); L.njobs = njobs;
-  L.packed = reinterpret_cast<act_t*>(packed); L.tgt = tgt; L.tgt_packed = reinterpret_cast<act_t*>(tgt_packed);
-  L.tfreq = tfreq < 1 ? 1 : tfreq;
-  L.noise = noise; L.eff = eff; L.gnoise = gnoise; L.noise_dst = noise_dst; L.noise_n = noise_n;
-  L.tnoise = tnoise; L.teff = teff; L.tpk = reinterpret_cast<act_t*>(tpk); L.noise_rng = noise_rng; L.ff = ff;
-  L.part = part; L.wg = reinterpret_cast<const WgradGroup*>(wg); L.wg_blocks = wgm ? wg_blocks : 0;
-  L.dp = dpl;
-  switch (op) {
-    case -1: return optim_pack_op<-1>(L);
-    case 0: return optim_pack_op<0>(L);
-    case 1: return optim_pack_op<1>(L);
-    case 2: return optim_pack_op<2>(L);
-    case 3: return optim_pack_op<3>(L);
-    case 4: return optim_pack_op<4>(L);
-    case 5: return optim_pack_op<5>(L);
-    case 6: return optim_pack_op<6>(L);
-    case 7: return optim_pack_op<7>(L);
+  L.tfreq = a.tfreq < 1 ? 1 : a.tfreq;
+#define OP_CASE(N) case N: return optim_pack_op<N>(L);
+  switch (a.op) {
+    OP_CASE(-1) OP_CASE(0) OP_CASE(1) OP_CASE(2) OP_CASE(3) OP_CASE(4) OP_CASE(5) OP_CASE(6) OP_CASE(7)
     default: return false;
   }
+#undef OP_CASE
 }
 
 int upd_job_ints() { return (int)(sizeof(UpdJob) / sizeof(int)); }

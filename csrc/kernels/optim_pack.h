@@ -968,16 +968,17 @@ optim_pack_kernel(float* __restrict__ W, const float* __restrict__ G, float* __r
 }
 
 
-// All arguments of one optim_pack_kernel launch (the launcher in optim.hip fills it; the
-// per-optimizer instantiations live in optim_ops_*.hip so the build compiles them in parallel).
+// One optim_pack_kernel launch: the caller's arguments and what the launcher in optim.hip derives
+// from them (the per-optimizer instantiations live in optim_ops_*.hip so the build compiles them
+// in parallel).
 struct OptPackLaunch {
+  const OptimPackArgs& a;    // pass-through pointers are read from here
   int grid; size_t dyn; hipStream_t st;
   int mode; bool few;
-  float* w; const float* g; float* s0; float* s1; float* beta_pow; int64_t* step; int32_t* ticket; OptHP h;
-  const UpdJob* jobs; int njobs; act_t* packed; float* tgt; act_t* tgt_packed; int tfreq;
-  const float* noise; float* eff; const float* gnoise; float* noise_dst; int noise_n;
-  TrunkSample smp; PerStep per; const float* tnoise; float* teff; act_t* tpk; int64_t* noise_rng; FcFuse ff;
-  const float* part; const WgradGroup* wg; int wg_blocks; DpLaunch dp;
+  OptHP h;
+  int tfreq;                 // clamped to >= 1
+  TrunkSample smp; PerStep per; FcFuse ff; DpLaunch dp;   // the caller's, or empty
+  int wg_blocks;             // 0 unless the launch runs the weight-gradient tiles
 };
 
 // Launches the kernel of L.mode; false (nothing launched) when that mode is not instantiated.
@@ -999,11 +1000,13 @@ bool optim_pack_op(const OptPackLaunch& L);
 #ifdef DQN_OPTIM_DEFINE_OPS
 template <int N>
 bool optim_pack_op(const OptPackLaunch& L) {
-#define OPM(M) hipLaunchKernelGGL((optim_pack_kernel<N, (M)>), dim3(L.grid), dim3(kPackThreads), L.dyn, L.st, L.w, L.g, \
-                                  L.s0, L.s1, L.beta_pow, L.step, L.ticket, L.h, L.jobs, L.njobs, L.packed, L.tgt, \
-                                  L.tgt_packed, L.tfreq, L.noise, L.eff, L.gnoise, L.noise_dst, L.noise_n, L.smp, L.per, \
-                                  L.tnoise, L.teff, L.tpk, L.noise_rng, L.ff, L.part, L.wg, L.wg_blocks, \
-                                  L.dp)
+  const OptimPackArgs& a = L.a;
+#define OPM(M) hipLaunchKernelGGL((optim_pack_kernel<N, (M)>), dim3(L.grid), dim3(kPackThreads), L.dyn, L.st, a.w, a.g, \
+                                  a.s0, a.s1, a.beta_pow, a.step, a.ticket, L.h, static_cast<const UpdJob*>(a.jobs), \
+                                  a.njobs, static_cast<act_t*>(a.packed), a.tgt, static_cast<act_t*>(a.tgt_packed), \
+                                  L.tfreq, a.noise, a.eff, a.gnoise, a.noise_dst, a.noise_n, L.smp, L.per, a.tnoise, \
+                                  a.teff, static_cast<act_t*>(a.tpk), a.noise_rng, L.ff, a.part, \
+                                  static_cast<const WgradGroup*>(a.wg), L.wg_blocks, L.dp)
 #define OPM_CASE(M) case (M): OPM(M); return true;
   if constexpr (N < 0) {
     OPM(kModeNoisy);                                    // mix + pack only (noisy nets)

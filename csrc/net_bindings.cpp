@@ -5,18 +5,10 @@
 // dtype and device there, then hands raw device addresses to these entry
 // points, which only assemble the argument structs and launch on the current
 // HIP stream (so the whole step can be captured into one HIP graph).
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-
+#include "bind_common.h"
 #include "include/dqn_nets.h"
-#include "include/dqn_nets_k.h"
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
-
-template <typename T>
-T P(int64_t v) { return reinterpret_cast<T>(static_cast<intptr_t>(v)); }
 
 void pack(int64_t src, int64_t dst, int64_t jobs, int64_t njobs, int64_t max_threads, int64_t dst2, int64_t step,
           int64_t freq) {
@@ -452,15 +444,7 @@ void trunk(int64_t frames, std::vector<int64_t> ptrs, int64_t B, int64_t ninst, 
   // frame-stacked with k = 4 (int4 slot rows)
   if (!sample.empty()) {
     TORCH_CHECK(sample.size() == 17, "trunk sample: 16 pointers + sampled instances");
-    for (int i = 0; i < 16; ++i) TORCH_CHECK(sample[i] != 0, "trunk sample: null pointer");
-    dqn::TrunkSample& s = a.smp;
-    s.size = P<const int32_t*>(sample[0]); s.rng = P<int64_t*>(sample[1]); s.ticket = P<int32_t*>(sample[2]);
-    s.state_idx = P<const int32_t*>(sample[3]); s.next_idx = P<const int32_t*>(sample[4]);
-    s.actions = P<const int32_t*>(sample[5]); s.rewards = P<const float*>(sample[6]);
-    s.dones = P<const float*>(sample[7]); s.gammas = P<const float*>(sample[8]);
-    s.idx_out = P<int32_t*>(sample[9]); s.a_out = P<int32_t*>(sample[10]); s.r_out = P<float*>(sample[11]);
-    s.d_out = P<float*>(sample[12]); s.g_out = P<float*>(sample[13]);
-    s.st_slots = P<int32_t*>(sample[14]); s.nx_slots = P<int32_t*>(sample[15]);
+    dqn::TrunkSample& s = a.smp = trunk_sample(sample, "trunk");
     s.B = (int)B;
     s.ninst = (int)sample[16];
     TORCH_CHECK(B >= 1 && B <= 512 && s.ninst >= 1 && s.ninst <= ninst && a.frames != nullptr,

@@ -75,8 +75,8 @@ def main():
     op = kernel_op(opt)
 
     def launch(jobs, fcx, wgp=0, nb=0, sample=()):
-        ex.ext.optim_pack(op, *base, jobs, p, net.target.flat, pt, 1 << 30, ex.opt_max_grid, None, None, None, None,
-                          list(sample), [], [], None, None, None, None, fcx, 0, wg=wgp, wg_blocks=nb)
+        ex.ext.optim_pack(op, *base, jobs, p, target=net.target.flat, target_packed=pt, target_freq=1 << 30,
+                          max_grid=ex.opt_max_grid, sample=list(sample), fc=fcx, wg=wgp, wg_blocks=nb)
 
     def timeit(fn):
         for _ in range(10):

@@ -1,5 +1,6 @@
 """Every built native-extension variant (bf16 _C, fp16 _C_f16, fp32 _C_f32) imports, alone and
 all together in one process (module-local pybind types; -Bsymbolic kernel launchers)."""
+import ctypes
 import importlib
 import os
 
@@ -32,9 +33,29 @@ def test_ingest_server_binding_converts_lists():
         m.IngestServer(0, 1, 0, 4, 0.99, [0] * 7, [0] * 4, [0] * 3, [0] * 11, 0)
 
 
-# csrc/include/dqn_kernels.h launch_optim_pack (extern "C++": the Itanium-mangled name of its signature)
-_LAUNCH_OPTIM_PACK = ('_Z17launch_optim_packiPfPKfS_S_S_PlPiS1_ffifPKviPvS_S6_iiS1_S_S1_S_iPKN3dqn11TrunkSampleEPK7PerStep'
-                      'S1_S_S6_S2_PK6FcFuseS1_S5_iS5_S6_iP12ihipStream_t')
+# csrc/include/dqn_kernels.h: bool launch_optim_pack(const OptimPackArgs&, hipStream_t) (extern "C++": the
+# Itanium-mangled name of its signature) and OptimPackArgs, field by field
+_LAUNCH_OPTIM_PACK = '_Z17launch_optim_packRK13OptimPackArgsP12ihipStream_t'
+_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+
+
+class OptimPackArgs(ctypes.Structure):
+    _fields_ = [
+        # core buffers and hyper-parameters
+        ('op', _I), ('w', _P), ('g', _P), ('s0', _P), ('s1', _P), ('beta_pow', _P), ('step', _P), ('ticket', _P),
+        ('hp9', ctypes.POINTER(_F)), ('lr', _F), ('reg', _F), ('reg_end', _I), ('grad_scale', _F),
+        # job table and packed output
+        ('jobs', _P), ('njobs', _I), ('packed', _P), ('max_grid', _I), ('no_pack', _I), ('part', _P),
+        # target
+        ('tgt', _P), ('tgt_packed', _P), ('tfreq', _I), ('tsg', _P),
+        # noise
+        ('noise', _P), ('eff', _P), ('gnoise', _P), ('noise_dst', _P), ('noise_n', _I), ('noise_rng', _P),
+        ('tnoise', _P), ('teff', _P), ('tpk', _P),
+        # sampler
+        ('smp', _P), ('per', _P),
+        # fused gradients
+        ('fc', _P), ('wg', _P), ('wg_blocks', _I), ('dp', _P),
+    ]
 
 
 @pytest.mark.parametrize('name', ['_C', '_C_f16', '_C_f32'])
@@ -45,24 +66,21 @@ def test_optim_pack_launcher_refuses_unbuilt_modes(name):
     table (no jobs) and on the main table (> 256 jobs); so is an optimizer op that does not exist.
     Each returns false before any kernel is enqueued -- the call needs no GPU, and every device
     pointer it is given is null or never dereferenced."""
-    import ctypes as C
     if not _built(name):
         pytest.skip('native extension not built')
-    lib = C.CDLL(importlib.import_module('dist_dqn_amd.' + name).__file__)
+    mod = importlib.import_module('dist_dqn_amd.' + name)
+    assert ctypes.sizeof(OptimPackArgs) == mod.OPTIM_PACK_ARGS_BYTES, 'OptimPackArgs: field list out of step'
+    lib = ctypes.CDLL(mod.__file__)
     assert hasattr(lib, _LAUNCH_OPTIM_PACK), 'launch_optim_pack: signature changed, update the mangled name'
-    P, I, F = C.c_void_p, C.c_int, C.c_float
     fn = getattr(lib, _LAUNCH_OPTIM_PACK)
-    fn.restype = C.c_bool
-    fn.argtypes = [I] + [P] * 8 + [F, F, I, F, P, I, P, P, P, I, I, P, P, P, P, I] + [P] * 9 + [I, P, P, I, P]
-    hp9 = (C.c_float * 9)()
+    fn.restype = ctypes.c_bool
+    fn.argtypes = [ctypes.POINTER(OptimPackArgs), _P]
+    hp9 = (_F * 9)()
 
     def launch(op, njobs, tnoise):
-        # op, w g s0 s1 beta_pow step ticket, hp9, lr reg reg_end grad_scale, jobs njobs, packed tgt tgt_packed,
-        # tfreq max_grid, noise eff gnoise noise_dst noise_n, smp per, tnoise teff tpk noise_rng fc part wg,
-        # wg_blocks, dp tsg, no_pack, stream
-        return fn(op, *[None] * 7, C.cast(hp9, P), 0.1, 0.0, 0, 1.0, None, njobs, None, None, None, 1, 2048,
-                  None, None, None, None, 0, None, None, tnoise, None, None, None, None, None, None, 0, None, None, 0,
-                  None)
+        a = OptimPackArgs()                  # zeroed: everything else absent
+        a.op, a.njobs, a.max_grid, a.hp9, a.tnoise = op, njobs, 2048, hp9, tnoise
+        return fn(ctypes.byref(a), None)
 
     assert launch(0, 0, 16) is False         # RMSProp-class op 0, few-block table (16-bit builds)
     assert launch(0, 300, 16) is False       # main table

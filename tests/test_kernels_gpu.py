@@ -285,3 +285,35 @@ def test_optim_pack_refuses_a_mode_it_does_not_build():
                        f32(64), f32(n), pk(), None, [], 0)
     torch.cuda.synchronize()
     assert int(step) == 0 and not w.any() and not tgt.any()
+
+
+def test_optim_pack_defaults_mean_absent():
+    """Every ``optim_pack`` parameter after ``packed`` but ``max_grid`` may be left out: one plain SGD
+    update (op 0) of 2048 floats through one elementwise job, launched with every absent argument
+    spelled out positionally and again with the required arguments only, leaves bit-equal state --
+    and the state the update rule gives, so neither call was a no-op."""
+    from dist_dqn_amd.ops import _ext
+    from dist_dqn_amd.ops.executor import _UpdJob
+    ext = _ext.load(required=True)
+    n, lr = 2048, 0.1
+    grad = torch.full((n,), 3.0, device=DEV)
+    jobs = torch.tensor(_UpdJob(kind=1, src_off=0, K=n, fwd_off=-1).ints(), dtype=torch.int32, device=DEV)
+    assert jobs.numel() == ext.UPD_JOB_INTS
+
+    def run(*tail, **kw):
+        w, s0, s1 = (torch.zeros(n, device=DEV) for _ in range(3))
+        step = torch.zeros(1, dtype=torch.int64, device=DEV)
+        packed = torch.zeros(256, dtype=torch.bfloat16, device=DEV)
+        ext.optim_pack(0, w, grad, s0, s1, torch.zeros(2, device=DEV),
+                       torch.zeros(17 * 32, dtype=torch.int32, device=DEV), lr, 0.0, 0, 1.0, step, [0.0] * 9, jobs,
+                       packed, *tail, **kw)
+        torch.cuda.synchronize()
+        return w, packed, s0, s1, step
+
+    spelled = run(None, None, 1, 2048, None, None, None, None, [], [], [], None, None, None, None, [], 0, 0, 0, [], 0,
+                  False)
+    short = run(max_grid=2048)
+    for a, b in zip(spelled, short):
+        assert torch.equal(a, b)
+    assert int(short[4]) == 1
+    assert torch.equal(short[0], -(torch.full((n,), lr, device=DEV) * grad))
