@@ -4,8 +4,10 @@
 // launch boundary and h re-read it removes.
 //
 // Block = one 16-row x 16-column tile of h for one instance (8 waves: split-K over the 3136-deep
-// K, LDS reduce; the igemm fc tiling). Its epilogue stores the bf16 h tile and immediately folds
-// it into the output layer: partial Q[r][a] = sum_{16 cols} h[r][c] W2[c][a] (dueling: value tiles
+// K, LDS reduce; the igemm fc tiling). Waves 0..3 reduce the eight partial tiles (one accumulator
+// register, i.e. four whole rows, each), store the bf16 h rows and immediately fold them into the
+// output layer with no block barrier in between:
+// partial Q[r][a] = sum_{16 cols} h[r][c] W2[c][a] (dueling: value tiles
 // into column A), one write-through store per value into the tile's own slot of
 // [instance][row][32][tile] (the tail sums the slots in tile order: bit-reproducible). Each
 // block then arrives on its row group's counter once its write-through h stores and atomics have
@@ -39,16 +41,15 @@ constexpr int kFoldMaxHid = 512;
 constexpr int kFoldU1 = DQN_ACT_F32 ? 7 : 13, kFoldU2 = DQN_ACT_F32 ? 4 : 8;
 
 struct FoldLds {
-  float red[7 * 256];                          // split-K partial tiles of waves 1..7
+  float red[8 * 256];                          // split-K partial tiles of the 8 waves
   float ht[16][17];                            // the tile's h (bf16-rounded, as stored)
   act_t hv[16][16];                            // the tile's h as stored
   float w2t[16 * kFoldMaxA];                   // the tile's rows of the output layer (fold)
   float w2[kFoldMaxHid * kFoldMaxA + kFoldMaxHid];   // tail: online output layer (+ value column)
-  float q[3][17][33];                          // tail: Q rows per instance (+ the bias row)
+  float q[3][16][33];                          // tail: Q rows per instance
   float dq[16][33];                            // tail: dQ rows (| dV at A)
   int32_t pst[16][4];                          // actor tail: the envs' frame stacks
   int flag;
-  int timed_out;                               // dH-tile block: the dQ wait expired
 };
 
 template <int AT, int kFoldU>
@@ -92,7 +93,9 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
   };
   load_batch(ks_lo);
   int e0 = 0;                                   // the group's dQ epoch before this launch's tail
-  if (dh_tile) e0 = __hip_atomic_load(f.dq_epoch + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // (every learner block: whichever arrives last publishes e0 + 1, without re-reading the word)
+  if (f.spin && !actor_inst)
+    e0 = __hip_atomic_load(f.dq_epoch + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const bool frames_duty = actor_inst && nt < h.act_E;
   // the frame duty's rng / cursor words (before the arrival: the tail advances them); scalars,
   // not an ActorPre (whose per-thread stack array put 88 bytes per lane in scratch)
@@ -111,12 +114,18 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
   // what the group's tail reads besides the other blocks' results, loaded now by every block (any
   // block may turn out to be the last arriver): the output-layer biases of the group's instances
   // and the TD inputs of its rows
-  float pb = 0.f;                               // bias of (instance tid / 32, column tid % 32)
+  // (the bias of the tail's Q entries this thread sums: entry t = (instance, row, column), t = tid
+  //  and tid + kFoldThreads -- 3 * 16 * 19 entries at most)
+  float pb[2] = {0.f, 0.f};
   {
-    const int ni_ = actor_inst ? 1 : f.nlearn, i = tid >> 5, c = tid & 31;
-    if (i < ni_) {
-      const int bw = actor_inst ? 0 : i;
-      pb = c < A ? h.b[bw][c] : (c == A && h.dueling ? h.bv[bw][0] : 0.f);
+    const int ni_ = actor_inst ? 1 : f.nlearn;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int t = tid + k * kFoldThreads;
+      if (t < ni_ * 16 * A1) {
+        const int i = t / (16 * A1), c = (t - i * 16 * A1) % A1, bw = actor_inst ? 0 : i;
+        pb[k] = c < A ? h.b[bw][c] : (h.dueling ? h.bv[bw][0] : 0.f);
+      }
     }
   }
   float tr = 0.f, tg = 0.f, tdn = 0.f, tw = 1.f;
@@ -133,62 +142,52 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
 #pragma unroll
     for (int u = 0; u < kFoldU; ++u) acc = mfma16(af[u], bf[u], acc);
   }
-  if (wave > 0) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) S.red[(wave - 1) * 256 + r * 64 + lane] = acc[r];
-  }
+  for (int r = 0; r < 4; ++r) S.red[wave * 256 + r * 64 + lane] = acc[r];
   __syncthreads();
   FOLD_MARK(1);
-  if (wave == 0) {
+  // ---- reduce, epilogue, h stores and fold on waves 0..3: wave w owns accumulator register w of
+  //      the C/D layout (col = lane & 15, row = 4 * (lane >> 4) + w), i.e. four whole rows of the
+  //      tile, so the fold of those rows needs this wave's LDS writes only -- no block barrier
+  //      between the reduce and the partial-Q stores. The slices are summed in wave order.
+  if (wave < 4) {
+    float v32 = S.red[wave * 64 + lane];
 #pragma unroll
-    for (int s = 0; s < 7; ++s)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += S.red[s * 256 + r * 64 + lane];
-    // epilogue: C/D layout col = lane & 15, row = 4 * (lane >> 4) + r
+    for (int s = 1; s < 8; ++s) v32 += S.red[s * 256 + wave * 64 + lane];
     const int col = lane & 15, n = nt * 16 + col;
-    const float scale = a.scale[inst], bv = a.bias[inst][n];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 4 * (lane >> 4) + r, m = m_base + row;
-      const act_t v = (act_t)fmaxf(acc[r] * scale + bv, 0.f);
-      S.hv[row][col] = v;
-      S.ht[row][col] = m < Mi ? (float)v : 0.f;
-    }
-  }
-  __syncthreads();
-  // the h tile leaves as write-through 32-bit stores (agent scope, relaxed): the group's tail
-  // reads it from another CU / XCD after the counter, with no L2 write-back fence on this side
-  {
+    const int row = 4 * (lane >> 4) + wave, m = m_base + row;
+    const act_t v = (act_t)fmaxf(v32 * a.scale[inst] + a.bias[inst][n], 0.f);
+    S.hv[row][col] = v;
+    S.ht[row][col] = m < Mi ? (float)v : 0.f;
+    // the h tile leaves as write-through 32-bit stores (agent scope, relaxed): the group's tail
+    // reads it from another CU / XCD after the counter, with no L2 write-back fence on this side
     constexpr int kPer = 4 / (int)sizeof(act_t);             // act_t per 32-bit word
-    constexpr int kWords = 16 * 16 / kPer;
-    if (tid < kWords) {
-      const int row = tid / (16 / kPer), c0 = (tid - row * (16 / kPer)) * kPer, m = m_base + row;
-      if (m < a.M) {
-        uint32_t wv;
-        __builtin_memcpy(&wv, &S.hv[row][c0], 4);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(reinterpret_cast<act_t*>(a.out[inst]) + (int64_t)m * a.ldo +
-                                                    nt * 16 + c0);
-        __hip_atomic_store(dst, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+    uint32_t wv = 0;
+    __builtin_memcpy(&wv, &v, sizeof(act_t));
+    if constexpr (kPer == 2) wv |= (uint32_t)__shfl_down((int)wv, 1) << 16;
+    if (col % kPer == 0 && m < a.M) {
+      uint32_t* dst = reinterpret_cast<uint32_t*>(reinterpret_cast<act_t*>(a.out[inst]) + (int64_t)m * a.ldo + n);
+      __hip_atomic_store(dst, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-  }
-  // ---- fold: partial output layer of this tile (value tiles: the first HID units, dueling)
-  {
-    if (tid < 16 * A1) {
-      const int row = tid / A1, c = tid - row * A1;
+    // ---- fold: partial output layer of this tile (value tiles: the first HID units, dueling) over
+    //      the wave's own four rows (its S.ht writes above, ordered within the wave)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int t = lane; t < 4 * A1; t += 64) {
+      const int g = t / A1, c = t - g * A1, frow = 4 * g + wave;
       const bool mine = vtile ? c == A : c < A;
-      if (mine && m_base + row < Mi) {
+      if (mine && m_base + frow < Mi) {
         float s = 0.f;
         if (vtile) {
 #pragma unroll
-          for (int j = 0; j < 16; ++j) s += S.ht[row][j] * S.w2t[j];
+          for (int j = 0; j < 16; ++j) s += S.ht[frow][j] * S.w2t[j];
         } else {
 #pragma unroll
-          for (int j = 0; j < 16; ++j) s += S.ht[row][j] * S.w2t[j * A + c];
+          for (int j = 0; j < 16; ++j) s += S.ht[frow][j] * S.w2t[j * A + c];
         }
         // this tile's partial, a write-through store into its own slot: the tail sums the slots
         // in a fixed order (bit-reproducible, no fp32 atomics)
-        __hip_atomic_store(f.qacc + (((int64_t)inst * f.Mpad + m_base + row) * 32 + c) * gridDim.y + nt, s,
+        __hip_atomic_store(f.qacc + (((int64_t)inst * f.Mpad + m_base + frow) * 32 + c) * gridDim.y + nt, s,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -241,41 +240,45 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
     // wait for the group's tail to publish dQ (every block of the launch is resident: spin mode)
     // (no acquire fence here: an L2 invalidation per waiting block costs the next launches their
     //  cached weights; the dQ rows are read with agent-scope loads, coherent like the stores)
-    if (tid == 0) {
-      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      S.timed_out = 0;
-      while (__hip_atomic_load(f.dq_epoch + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == e0) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 100000000ull) {      // 1 s: never hang, never
-          S.timed_out = 1;                                                 // train on stale dQ
-          if (f.err != nullptr)
-            __hip_atomic_store(f.err, 0x1000000 | (int)blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
+    // Wave 0 polls (lane 0) and then loads the rows itself: one block barrier between the epoch and
+    // the dH tile instead of two.
+    if (wave == 0) {
+      int timed_out = 0;
+      if (lane == 0) {
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        while (__hip_atomic_load(f.dq_epoch + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == e0) {
+          __builtin_amdgcn_s_sleep(1);
+          if (__builtin_amdgcn_s_memrealtime() - t0 > 100000000ull) {      // 1 s: never hang, never
+            timed_out = 1;                                                   // train on stale dQ
+            if (f.err != nullptr)
+              __hip_atomic_store(f.err, 0x1000000 | (int)blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+          }
         }
       }
-    }
-    __syncthreads();
-    // timed out (flagged: the learner's device check raises): the tile is written as ZEROS -- the
-    // group then adds nothing to this step's gradient, instead of the previous step's stale dH
-    const int nr = S.timed_out ? 0 : min(16, a.M - m_base);
-    for (int t = tid; t < 16 * A1; t += kFoldThreads) {
-      const int r = t / A1, c = t - r * A1;
-      S.dq[r][c] = r < nr ? __hip_atomic_load(f.dqg + (int64_t)(m_base + r) * 32 + c, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT)
-                          : 0.f;
+      timed_out = __builtin_amdgcn_readfirstlane(timed_out);
+      // (the row loads stay behind the epoch load: workgroup scope, no cache invalidation)
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      // timed out (flagged: the learner's device check raises): the tile is written as ZEROS -- the
+      // group then adds nothing to this step's gradient, instead of the previous step's stale dH
+      const int nr = timed_out ? 0 : min(16, a.M - m_base);
+      for (int t = lane; t < 16 * A1; t += 64) {
+        const int r = t / A1, c = t - r * A1;
+        S.dq[r][c] = r < nr ? __hip_atomic_load(f.dqg + (int64_t)(m_base + r) * 32 + c, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT)
+                            : 0.f;
+      }
     }
     __syncthreads();
     dh_from(S.dq);
     return;
   }
-  if (tid == 0) {
-    // acquire, then plain loads of the partial-Q slots (and, not spin, the other blocks' h rows).
-    // (round 5 measured sc1 slot loads without the fence 0.3-0.6 us slower, gpurun_out/r5v: removed)
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(f.cnt + grp, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
+  // acquire, then plain loads of the partial-Q slots (and, not spin, the other blocks' h rows).
+  // Every wave issues the fence itself (the flag barrier above orders it after thread 0's counter
+  // read): its slot loads follow at once, not a second block barrier behind thread 0's fence.
+  // (round 5 measured sc1 slot loads without the fence 0.3-0.6 us slower: removed)
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (tid == 0) __hip_atomic_store(f.cnt + grp, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
   // ---- tail: every load it needs is issued at once -- the online h rows (dH mask, registers),
   //      the online output layer (LDS) and the group's partial-Q slots -- then Q, biases, dueling
@@ -300,42 +303,47 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
   {
     // Q rows: every (instance, row, column) sums its tiles' partial slots in tile order (dueling:
     // advantage columns over the advantage tiles, the value column over the value tiles), + bias
+    // (an entry's slots -- at most kFoldMaxHid / 16 = 32 -- are all loaded before the first add)
     const int NT = (int)gridDim.y, half = h.dueling ? NT / 2 : 0;
-    if (tid < ni * 32) S.q[tid >> 5][16][tid & 31] = pb;          // (row 16: the bias row)
-    for (int t = tid; t < ni * 16 * A1; t += kFoldThreads) {
+    constexpr int kQv = kFoldMaxHid / 16 / 4;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int t = tid + k * kFoldThreads;
+      if (t >= ni * 16 * A1) break;
       const int i = t / (16 * A1), rem = t - i * 16 * A1, r = rem / A1, c = rem - r * A1;
       float v = 0.f;
       if (r < nrows && (c < A || h.dueling)) {
-        const int pb0 = 4 * (int)((((int64_t)(i0 + i) * f.Mpad + m_base + r) * 32 + c) * NT);   // byte offset
         const int lo = h.dueling ? (c < A ? half : 0) : 0, hi = h.dueling ? (c < A ? NT : half) : NT;
-        const float* p = f.qacc + pb0 / 4;         // (summed in tile order)
-        for (int u = lo; u < hi; u += 4) {
-          const float4 x = *reinterpret_cast<const float4*>(p + u);
-          v += x.x;
-          v += x.y;
-          v += x.z;
-          v += x.w;
-        }
+        const float* p = f.qacc + (((int64_t)(i0 + i) * f.Mpad + m_base + r) * 32 + c) * NT + lo;
+        float4 x[kQv];
+#pragma unroll
+        for (int u = 0; u < kQv; ++u)
+          x[u] = lo + 4 * u < hi ? *reinterpret_cast<const float4*>(p + 4 * u) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < kQv; ++u)             // (summed in tile order)
+          if (lo + 4 * u < hi) {
+            v += x[u].x;
+            v += x[u].y;
+            v += x[u].z;
+            v += x[u].w;
+          }
       }
-      S.q[i][r][c] = v;
+      S.q[i][r][c] = v + pb[k];
     }
   }
   FOLD_MARK(4);
   __syncthreads();
-  if (tid < ni * 16) {
-    const int i = tid >> 4, r = tid & 15;
-    float* q = S.q[i][r];
-    const float* bq = S.q[i][16];
-    for (int c = 0; c < A; ++c) q[c] += bq[c];
-    if (h.dueling) {
-      const float v = q[A] + bq[A];
+  if (h.dueling) {                               // (plain heads: the biased sums are the Q rows)
+    if (tid < ni * 16) {
+      float* q = S.q[tid >> 4][tid & 15];
+      const float v = q[A];
       float mean = 0.f;
       for (int c = 0; c < A; ++c) mean += q[c];
       mean /= (float)A;
       for (int c = 0; c < A; ++c) q[c] += v - mean;
     }
+    __syncthreads();
   }
-  __syncthreads();
 
   if (actor_inst) {
     // ---- fused acting: decision + replay append per env, state advance, PER insert
@@ -355,8 +363,13 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
     return;
   }
 
-  // ---- learner: TD target, loss, dQ, priorities (thread per row)
-  float contrib = 0.f;
+  // ---- learner: TD target, loss, dQ, priorities (thread per row). The row's thread also publishes
+  //      its dQ row (spin mode; write-through): every row lives in wave 0, whose s_waitcnt covers
+  //      the whole group's rows, so the epoch follows with no block barrier and no reload (the
+  //      word is e0 + 1: only this block writes it in this launch). The online blocks waiting on
+  //      it write their dH tiles (this block too, below, when it is one of them).
+  const bool publish = f.spin && !f.dbg_no_publish;
+  float contrib = 0.f, ad0 = 0.f;
   if (tid < nrows) {
     const int b = m_base + tid;
     const float td = tdn;
@@ -382,33 +395,29 @@ __global__ void __launch_bounds__(kFoldThreads, kFoldU == kFoldU2 ? 4 : 2) fc_he
     const float gsc = tw * dper / (float)h.B;
     // Q_i = V + A_i - mean(A): dV = sum_i dQ_i, dA_i = dQ_i - mean(dQ)
     const float sub = h.dueling ? gsc / (float)A : 0.f;
-    for (int i = 0; i < A; ++i) S.dq[tid][i] = ((i == ta) ? gsc : 0.f) - sub;
-    S.dq[tid][A] = h.dueling ? gsc : 0.f;
-    h.prio[b] = fabsf(d);
+    float* gq = f.dqg + (int64_t)b * 32;
+    for (int i = 0; i <= A; ++i) {
+      const float v = i < A ? ((i == ta) ? gsc : 0.f) - sub : (h.dueling ? gsc : 0.f);
+      S.dq[tid][i] = v;
+      if (publish) __hip_atomic_store(gq + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    ad0 = fabsf(d);
   }
+  // (stamp 5 is read here and stored after the publish: its store is not one the s_waitcnt waits for)
+  const int64_t t5 = prof ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
   if (wave == 0) {
+    if (publish) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0)
+        __hip_atomic_store(f.dq_epoch + blockIdx.x, e0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid < nrows) h.prio[m_base + tid] = ad0;
     const float sum = wave_sum(contrib);
     if (lane == 0) h.loss_parts[blockIdx.x] = sum;       // summed by the fc dgrad launch
   }
-  FOLD_MARK(5);
+  if (prof) prof[5] = t5;
   __syncthreads();
-  if (f.spin && !f.dbg_no_publish) {
-    // publish the group's dQ rows (write-through), then its epoch: the online blocks waiting on it
-    // write their dH tiles (this block too, when it is one of them)
-    const int g = (int)blockIdx.x;
-    for (int t = tid; t < nrows * A1; t += kFoldThreads) {
-      const int r = t / A1, c = t - r * A1;
-      __hip_atomic_store(f.dqg + (int64_t)(m_base + r) * 32 + c, S.dq[r][c], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const int e = __hip_atomic_load(f.dq_epoch + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(f.dq_epoch + g, e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (dh_tile) dh_from(S.dq);
-  }
+  if (publish && dh_tile) dh_from(S.dq);
   for (int t = tid; t < nrows * 64; t += kFoldThreads) {
     const int r = t >> 6, c = t & 63;
     const float g = c < A ? S.dq[r][c] : (c == 32 && h.dueling ? S.dq[r][A] : 0.f);
