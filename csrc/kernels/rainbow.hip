@@ -278,7 +278,9 @@ __global__ void __launch_bounds__(kC51Threads) c51_train_kernel(HeadArgs a) {
     // 3. projection onto the support: each atom's mass to its floor / ceil neighbours through
     //    LDS float atomics into this wave's own row (in-order within the wave: no barrier)
     const float tz = fminf(fmaxf(rw + gm * z, a.vmin), a.vmax);
-    const float bj = fminf((tz - a.vmin) / dz, (float)(NA - 1));
+    // (fp32 (vmax - vmin) / dz is not always NA - 1: 62.999996 for [-10, 10] with 64 atoms,
+    //  61.000004 for [-1, 1] with 62 -- a target clamped to vmax sits on the last atom exactly)
+    const float bj = tz >= a.vmax ? (float)(NA - 1) : fminf((tz - a.vmin) / dz, (float)(NA - 1));
     float* mr = mrow[wave];
     mr[lane] = 0.f;
     if (on) {

@@ -98,7 +98,9 @@ td_loss_c51_kernel(const float* __restrict__ lg, const float* __restrict__ lgn_t
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
     const float tz = fminf(fmaxf(rew[b] + gam[b] * (1.f - done[b]) * z, vmin), vmax);
-    const float bpos = (tz - vmin) / dz;
+    // (fp32 (vmax - vmin) / dz is not always N - 1: above it the ceil neighbour would leave the
+    //  row, below it a target clamped to vmax would leak mass to atom N - 2)
+    const float bpos = tz >= vmax ? (float)(N - 1) : fminf((tz - vmin) / dz, (float)(N - 1));
     const float lo = floorf(bpos), hi = ceilf(bpos);
     if (on) {
       const int l = (int)lo, u = (int)hi;

@@ -54,7 +54,12 @@ def categorical_projection(p_next: torch.Tensor, rewards: torch.Tensor, dones: t
     dz = (v_max - v_min) / (N - 1)
     tz = (rewards.float().view(B, 1) + gamma * (1.0 - dones.float().view(B, 1)) * z.view(1, N))
     tz = tz.clamp(v_min, v_max)
-    b = (tz - v_min) / dz
+    top = float(torch.tensor(v_max, dtype=tz.dtype))        # v_max as tz holds it (host scalar)
+    # fp32 (v_max - v_min) / dz is not always N - 1 (61.000004 for [-1, 1] with 62 atoms: the
+    # ceil neighbour would be index N; 62.999996 for [-10, 10] with 64: a target clamped to
+    # v_max would leak mass to atom N - 2), so, as the HIP kernels do, a clamped target sits on
+    # the last atom exactly and nothing lies beyond it
+    b = ((tz - v_min) / dz).clamp(max=N - 1).masked_fill(tz >= top, N - 1)
     lo = b.floor().long()
     hi = b.ceil().long()
     m = torch.zeros(B, N, device=p_next.device)

@@ -8,7 +8,9 @@ production head kernels' loss / dL/dQ against a loss computed purely in torch.
 * the same against the pure-torch fp32 oracle gradient of the fc layer;
 * head_loss_kernel / c51_train_kernel: loss, dL/dQ (dL/dlogits) and dH of the kernel vs torch
   autograd of ``models/losses.py`` on the very hidden rows the kernel consumed (fp32 output
-  layer in torch; the kernel's output layer runs on bf16 MFMA fragments);
+  layer in torch; the kernel's output layer runs on bf16 MFMA fragments); the C51 head also
+  dueling (value logits at other VO offsets of the one igemm over [W | Wv]), at 5, 6 and 18
+  actions, 32 and 62 atoms, and on a support whose fp32 ``(v_max - v_min) / dz`` exceeds N - 1;
 * deterministic conv weight gradients (``--det_wgrad``: chunk-group partials summed by the
   optimizer launch in a fixed order): two identical runs are bit-identical, the result matches
   the fp32-atomics path to summation order and the fp32 oracle's conv gradients.
@@ -246,6 +248,28 @@ def _head_torch(net, ws, B, batch, dist):
         # the kernels hand the advantage stream's dL/dA = dQ - mean(dQ) to the output layer
         dq = o0.grad
         return float(loss), dq - dq.mean(1, keepdim=True), h0.grad * (hs[0] > 0).float()
+    if ex.dueling and dist:
+        # dueling C51: advantage logits from h's advantage half, value logits from its value half,
+        # combined per atom; dout in the kernel's row layout [A * atoms | pad | value at VO | pad]
+        H, N, v = ex.HID, ex.atoms, net.arch
+
+        def lg_of(h, f):
+            val = h[:, :H] @ T(f, 'value/output/w', H, N) + T(f, 'value/output/b', N)
+            adv = (h[:, H:] @ T(f, 'advantage/output/w', H, A * N) + T(f, 'advantage/output/b', A * N)).view(B, A, N)
+            return adv, val
+        comb = lambda adv, val: adv + val.unsqueeze(1) - adv.mean(1, keepdim=True)
+        h0 = hs[0].detach().requires_grad_(True)
+        a0, v0 = lg_of(h0, flats[0])
+        a0.retain_grad()
+        v0.retain_grad()
+        outs = [None] + [comb(*lg_of(h, f)).detach() for h, f in zip(hs[1:], flats[1:])]
+        loss, _ = losses.c51_loss(comb(a0, v0), batch['actions'], batch['rewards'], batch['dones'], outs[1],
+                                  outs[2] if ex.double else None, batch['gammas'].view(-1, 1), v.v_min, v.v_max)
+        loss.backward()
+        dout = torch.zeros(B, ex.c51_KD, device=h0.device)
+        dout[:, :A * N] = a0.grad.reshape(B, A * N)
+        dout[:, ex.c51_VO:ex.c51_VO + N] = v0.grad
+        return float(loss.detach()), dout, h0.grad * (hs[0] > 0).float()
     W = lambda f: f[lay.offsets['output/w']:lay.offsets['output/w'] + lay.numel('output/w')].view(HH, -1)
     bias = lambda f: f[lay.offsets['output/b']:lay.offsets['output/b'] + lay.numel('output/b')]
     outs = [h @ W(f) + bias(f) for h, f in zip(hs, flats)]
@@ -266,11 +290,19 @@ def _head_torch(net, ws, B, batch, dist):
     return float(loss), dout, dh
 
 
-@pytest.mark.parametrize('extra,fold', [('', True), ('', False), ('--double_dqn --loss=huber', True),
-                                        ('--double_dqn --loss=huber', False), ('--dueling --double_dqn', True),
-                                        ('--dueling', False), ('--distributional', False),
-                                        ('--distributional --double_dqn', False)])
-def test_head_kernels_match_pure_torch_loss(extra, fold):
+_HEAD_CASES = [('', True), ('', False), ('--double_dqn --loss=huber', True),
+               ('--double_dqn --loss=huber', False), ('--dueling --double_dqn', True),
+               ('--dueling', False), ('--distributional', False),
+               ('--distributional --double_dqn', False)]
+# the C51 head through the one igemm over [W | Wv], at other VO offsets of the packed output layer
+_C51_HEAD_CASES = [('--distributional --dueling --double_dqn', 6), ('--distributional --dueling --double_dqn', 18),
+                   ('--distributional --dueling --num_atoms=32', 5),
+                   ('--distributional --v_min=-1 --v_max=1 --num_atoms=62 --double_dqn', 6)]
+
+
+@pytest.mark.parametrize('extra,fold,A', [pytest.param(e, f, 6, id='%s-%s' % (e, f)) for e, f in _HEAD_CASES] +
+                         [pytest.param(e, False, A, id='%s-False-%d' % (e, A)) for e, A in _C51_HEAD_CASES])
+def test_head_kernels_match_pure_torch_loss(extra, fold, A):
     """The scalar head folded into the fc launch (fc_head.hip, fold) / head_loss_kernel /
     c51_train_kernel vs torch autograd on the same hidden rows: the loss, the dL/dQ
     (dL/dlogits) rows the kernel hands to the output layer's weight gradient, and dH."""
@@ -278,7 +310,7 @@ def test_head_kernels_match_pure_torch_loss(extra, fold):
     from dist_dqn_amd.models.network import Network
     B = 32
     cfg = preset('nature', 'Pong-v0', '--seed=3 --backend=hip --dtype=bf16 %s' % extra)
-    net = Network.create_network(cfg, (84, 84, 4), 6, device=DEV)
+    net = Network.create_network(cfg, (84, 84, 4), A, device=DEV)
     g = torch.Generator(device=DEV).manual_seed(4)
     net.online.flat.normal_(0.0, 0.03, generator=g)
     net.target.flat.normal_(0.0, 0.03, generator=g)
@@ -286,7 +318,7 @@ def test_head_kernels_match_pure_torch_loss(extra, fold):
     batch = {
         'states': torch.randint(0, 256, (B, 84, 84, 4), dtype=torch.uint8, device=DEV, generator=g),
         'next_states': torch.randint(0, 256, (B, 84, 84, 4), dtype=torch.uint8, device=DEV, generator=g),
-        'actions': torch.randint(0, 6, (B,), dtype=torch.int32, device=DEV, generator=g),
+        'actions': torch.randint(0, A, (B,), dtype=torch.int32, device=DEV, generator=g),
         'rewards': torch.randn(B, device=DEV, generator=g) * 5.0,
         'dones': (torch.rand(B, device=DEV, generator=g) < 0.2).float(),
         'gammas': torch.full((B,), 0.99, device=DEV),
