@@ -12,9 +12,11 @@
 //                      B fragments read as one 16-byte load per lane; epilogues fuse
 //                      input scale + bias + ReLU (forward) or the ReLU mask (dgrad);
 //                      optional split-K across the waves of a block (LDS reduce);
-//   * wgrad_kernel     dW[K][N] = sum_m A[m][K]^T dZ[m][N] with both operands staged
-//                      transposed in LDS (padded rows: conflict-free ds_read_b128),
-//                      bias gradient fused, fp32 atomics only across M-chunks;
+//   * wgrad_kernel     dW[K][N] = sum_m A[m][K]^T dZ[m][N] with both operands staged in LDS
+//                      (16-bit builds: row-major, swizzled ds_write_b128, operands through
+//                      transposed ds_read_b64_tr_b16; fp32 build: transposed with padded rows,
+//                      conflict-free ds_read_b128), bias gradient fused, fp32 atomics only
+//                      across M-chunks; built from wgrad_dev.h's tile parts;
 //   * head_loss_kernel output layer + dueling combine + TD loss + dQ + head backward
 //                      (dW, db, dH masked by ReLU) in ONE workgroup.
 #include <stdio.h>
@@ -399,15 +401,61 @@ __global__ void __launch_bounds__(256) dgrad_s2_kernel(ConvArgs a) {
 
 // ================================================================ weight grad
 // dW[k][n] (+)= scale * sum_{m in chunk} A[m][k] * dZ[m][n];  db[n] (+)= sum_m dZ[m][n]
-// grid: x = M-chunk (MC rows), y = K-range (KB), z = N-range (NB). ONE staging
-// pass per block: all global loads of the chunk are issued first (register
-// staging), then written TRANSPOSED to LDS ([k][m], [n][m], rows padded by 8
-// elements) so each lane's 8 consecutive m are one ds_read_b128; then
+// grid: x = M-chunk (MC rows), y = K-range (KB), z = N-range (NB). Per chunk ONE staging pass:
+// all global loads of the chunk are issued first (register staging), then written to LDS in the
+// build's layout (wgrad_dev.h WgradTile: row-major with transposed operand reads in the 16-bit
+// builds, transposed with padded rows and ds_read_b128 in the fp32 build); then
 // (KB/16)x(NB/16) output tiles x MC/32 MFMA k-steps. fp32 atomics only when
 // more than one M-chunk contributes to a weight.
-// Body shared by the per-layer launch and the grouped launch (one block = one
-// (M-chunk, K-range, N-range) tile; LDS passed in so a grouped kernel can carve
-// every member's staging from one buffer).
+// Bodies shared by the per-layer launch and the grouped launch (one block = one
+// (M-chunk group, K-range, N-range) tile; LDS passed in so a grouped kernel can carve
+// every member's staging from one buffer), composed of wgrad_dev.h's tile parts.
+//
+// Chunks c0 .. c0 + nch - 1 summed in registers in ascending order, then one set of stores
+// (atomics when g.atomic). nch == 1 is the plain one-chunk block; nch > 1 the deterministic
+// grouped mode (no atomics: the caller points dw / db at its partial slice).
+template <class LD, int MC, int KB, int NB>
+DQN_DEV void wgrad_block_sum(const ConvArgs& a, const WgradArgs& g, int c0, int by, int bz, act_t* lds, int nch) {
+  using Tl = WgradTile<MC, KB, NB>;
+  using L = WgradLoad<LD, MC, KB, NB, 256>;
+  constexpr int PERW = (KB / 16) * (NB / 16) / 4;
+  static_assert(!L::ZPART && (KB / 16) * (NB / 16) % 4 == 0 && NB <= 256, "tiling");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k_lo = by * KB, n_lo = bz * NB;
+  const bool dob = g.db != nullptr && by == 0;
+  const int r = tid % MC, p = tid / MC;
+  f32x4 acc[PERW];
+#pragma unroll
+  for (int i = 0; i < PERW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float dbs = 0.f;
+  for (int c = 0; c < nch; ++c) {
+    const int m = (c0 + c) * MC + r;
+    const LD ld(a, 0, m);
+    typename L::Raw ra[L::GA];
+    bfx8 vz[L::GZ];
+    L::fetch_a(ld, a, k_lo, p, ra);
+    L::fetch_z(a, g, m, n_lo, p, vz);
+    if (c > 0) __syncthreads();                  // the previous chunk's LDS reads are done
+    wg_stage<L, Tl>(a, k_lo, r, p, ra, vz, lds);
+    __syncthreads();
+    if (dob && tid < NB) dbs = Tl::template bias_sum<1, 8>(lds, tid, 0, dbs);
+    if (c + 1 < nch) wg_sweep<Tl, 4, PERW>(lds, wave, lane, acc);
+  }
+  // the last chunk's sweep tile by tile, each tile stored as it completes (a one-chunk block then keeps
+  // one tile's accumulator live, not PERW)
+  const bool atomic = g.atomic != 0;
+  if (dob && tid < NB) wg_store_db<WgStore::kPlain>(g, n_lo + tid, dbs, atomic);
+#pragma unroll
+  for (int i = 0; i < PERW; ++i) {
+    Tl::template sweep_tile<4>(lds, wave, lane, i, acc[i]);
+    wg_store_tile<WgStore::kPlain, NB, 4>(a, g, k_lo, n_lo, wave, lane, i, acc[i], atomic);
+  }
+}
+
+// The one-chunk block. fp32 build: its own text, the stage's transposed layout written out -- as the
+// one-chunk call of wgrad_block_sum the per-layer conv2 / conv3 kernels ran 2.3 % slower (13.27 ->
+// 13.58 us, 17.22 -> 17.62 us at B = 32: profiles/wgrad_parts.md), so this build keeps a second copy
+// of the loads, the transposed staging and sweep, and the stores.
 #if DQN_ACT_F32
 template <class LD, int MC, int KB, int NB>
 DQN_DEV void wgrad_block(const ConvArgs& a, const WgradArgs& g, int bx, int by, int bz, act_t* lds) {
@@ -497,191 +545,23 @@ DQN_DEV void wgrad_block(const ConvArgs& a, const WgradArgs& g, int bx, int by, 
 #else
 template <class LD, int MC, int KB, int NB>
 DQN_DEV void wgrad_block(const ConvArgs& a, const WgradArgs& g, int bx, int by, int bz, act_t* lds) {
-  using Tl = WgradTile<MC, KB, NB>;
-  constexpr int SA = Tl::SA, SZ = Tl::SZ;
-  constexpr int TPR = 256 / MC;                  // threads per staged row
-  constexpr int GA = KB / 8 / TPR, GZ = NB / 8 / TPR;
-  constexpr int TILES = (KB / 16) * (NB / 16), PERW = TILES / 4, KSTEPS = MC / 32;
-  static_assert(256 % MC == 0 && (KB / 8) % TPR == 0 && (NB / 8) % TPR == 0 && TILES % 4 == 0, "tiling");
-  act_t* At = lds;                               // [MC][SA]
-  act_t* Zt = lds + MC * SA;                     // [MC][SZ]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int m_lo = bx * MC, k_lo = by * KB, n_lo = bz * NB;
-  {
-    const int r = threadIdx.x % MC, p = threadIdx.x / MC;
-    const int m = m_lo + r;
-    const bool mok = m < a.M;
-    const act_t* dz = reinterpret_cast<const act_t*>(g.dz) + (int64_t)(mok ? m : 0) * g.ldz + n_lo;
-    LD ld(a, 0, m);
-    bfx8 va[GA], vz[GZ];
-#pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int k0 = k_lo + (p + i * TPR) * 8;
-      va[i] = sel8(k0 < a.K, ld.frag(min(k0, a.K - 8)));          // (clamped: no branch per load)
-    }
-#pragma unroll
-    for (int i = 0; i < GZ; ++i) {
-      const int c8 = (p + i * TPR) * 8;
-      const int cz = (n_lo + c8 < g.N ? n_lo + c8 : 0) - n_lo;     // masked groups read column 0
-      vz[i] = sel8(mok && n_lo + c8 < g.N, *reinterpret_cast<const bfx8*>(dz + cz));
-    }
-#pragma unroll
-    for (int i = 0; i < GA; ++i) *reinterpret_cast<bfx8*>(At + r * SA + (((p + i * TPR) * 8) ^ wsw(r))) = va[i];
-#pragma unroll
-    for (int i = 0; i < GZ; ++i) *reinterpret_cast<bfx8*>(Zt + r * SZ + (((p + i * TPR) * 8) ^ wsw(r))) = vz[i];
-  }
-  __syncthreads();
-  const bool atomic = g.atomic != 0;
-  if (g.db != nullptr && by == 0) {
-    for (int n = threadIdx.x; n < NB; n += 256) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int r = 0; r < MC; ++r) s += (float)Zt[r * SZ + (n ^ wsw(r))];
-      const int nn = n_lo + n;
-      if (nn < g.N) {
-        float* pdb = nn < g.nsplit ? g.db + nn : g.db2 + (nn - g.nsplit);
-        s *= kInvLossScale;
-        if (atomic) atomicAdd(pdb, s); else *pdb = s;
-      }
-    }
-  }
-  // operand lane map: k-group gq = lane >> 4 takes m rows {4 gq + q} (elements 0..3) and
-  // {16 + 4 gq + q} (elements 4..7) of each 32-row k-step -- the same permutation of the
-  // reduction index on both operands; one 32-lane half reads 8 consecutive rows per instruction
-  const int gq = lane >> 4, rq = (lane >> 2) & 3, cp = 4 * (lane & 3);
-  constexpr int NTt = NB / 16;
-#pragma unroll
-  for (int i = 0; i < PERW; ++i) {
-    const int tile = wave + 4 * i;
-    const int kt = tile / NTt, nt = tile - kt * NTt;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const act_t* pa = At + (4 * gq + rq) * SA + kt * 16 + (cp ^ wsw(4 * gq));
-    const act_t* pz = Zt + (4 * gq + rq) * SZ + nt * 16 + (cp ^ wsw(4 * gq));
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) {
-      const bfx8 af = join_tr(lds_tr16(pa + 32 * s * SA), lds_tr16(pa + (32 * s + 16) * SA));
-      const bfx8 bf = join_tr(lds_tr16(pz + 32 * s * SZ), lds_tr16(pz + (32 * s + 16) * SZ));
-      acc = mfma16(af, bf, acc);
-    }
-    const int n = n_lo + nt * 16 + (lane & 15);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = k_lo + kt * 16 + 4 * (lane >> 4) + r;
-      if (k < a.K && n < g.N) {
-        float* p = n < g.nsplit ? g.dw + (int64_t)k * g.nsplit + n
-                                : g.dw2 + (int64_t)k * (g.N - g.nsplit) + (n - g.nsplit);
-        const float v = acc[r] * (g.scale * kInvLossScale);
-        if (atomic) atomicAdd(p, v); else *p = v;
-      }
-    }
-  }
-}
-
-// Deterministic grouped mode (no atomics): chunks bx .. bx + nch - 1 summed in registers in
-// ascending order, then plain stores (the caller points dw / db at its partial slice)
-template <class LD, int MC, int KB, int NB>
-DQN_DEV void wgrad_block_det(const ConvArgs& a, const WgradArgs& g, int bx, int by, int bz, act_t* lds, int nch) {
-  using Tl = WgradTile<MC, KB, NB>;
-  constexpr int SA = Tl::SA, SZ = Tl::SZ;
-  constexpr int TPR = 256 / MC;                  // threads per staged row
-  constexpr int GA = KB / 8 / TPR, GZ = NB / 8 / TPR;
-  constexpr int TILES = (KB / 16) * (NB / 16), PERW = TILES / 4, KSTEPS = MC / 32;
-  static_assert(256 % MC == 0 && (KB / 8) % TPR == 0 && (NB / 8) % TPR == 0 && TILES % 4 == 0 && NB <= 256,
-                "tiling");
-  act_t* At = lds;                               // [MC][SA]
-  act_t* Zt = lds + MC * SA;                     // [MC][SZ]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k_lo = by * KB, n_lo = bz * NB;
-  const bool dob = g.db != nullptr && by == 0;
-  // operand lane map: k-group gq = lane >> 4 takes m rows {4 gq + q} (elements 0..3) and
-  // {16 + 4 gq + q} (elements 4..7) of each 32-row k-step -- the same permutation of the
-  // reduction index on both operands; one 32-lane half reads 8 consecutive rows per instruction
-  const int gq = lane >> 4, rq = (lane >> 2) & 3, cp = 4 * (lane & 3);
-  constexpr int NTt = NB / 16;
-  f32x4 acc[PERW];
-#pragma unroll
-  for (int i = 0; i < PERW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float dbs = 0.f;
-  for (int c = 0; c < nch; ++c) {
-    const int r = threadIdx.x % MC, p = threadIdx.x / MC;
-    const int m = (bx + c) * MC + r;
-    const bool mok = m < a.M;
-    const act_t* dz = reinterpret_cast<const act_t*>(g.dz) + (int64_t)(mok ? m : 0) * g.ldz + n_lo;
-    LD ld(a, 0, m);
-    bfx8 va[GA], vz[GZ];
-#pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int k0 = k_lo + (p + i * TPR) * 8;
-      va[i] = sel8(k0 < a.K, ld.frag(min(k0, a.K - 8)));          // (clamped: no branch per load)
-    }
-#pragma unroll
-    for (int i = 0; i < GZ; ++i) {
-      const int c8 = (p + i * TPR) * 8;
-      const int cz = (n_lo + c8 < g.N ? n_lo + c8 : 0) - n_lo;     // masked groups read column 0
-      vz[i] = sel8(mok && n_lo + c8 < g.N, *reinterpret_cast<const bfx8*>(dz + cz));
-    }
-    if (c > 0) __syncthreads();                  // the previous chunk's LDS reads are done
-#pragma unroll
-    for (int i = 0; i < GA; ++i) *reinterpret_cast<bfx8*>(At + r * SA + (((p + i * TPR) * 8) ^ wsw(r))) = va[i];
-#pragma unroll
-    for (int i = 0; i < GZ; ++i) *reinterpret_cast<bfx8*>(Zt + r * SZ + (((p + i * TPR) * 8) ^ wsw(r))) = vz[i];
-    __syncthreads();
-    if (dob && (int)threadIdx.x < NB) {
-#pragma unroll 8
-      for (int q = 0; q < MC; ++q) dbs += (float)Zt[q * SZ + ((int)threadIdx.x ^ wsw(q))];
-    }
-#pragma unroll
-    for (int i = 0; i < PERW; ++i) {
-      const int tile = wave + 4 * i;
-      const int kt = tile / NTt, nt = tile - kt * NTt;
-      const act_t* pa = At + (4 * gq + rq) * SA + kt * 16 + (cp ^ wsw(4 * gq));
-      const act_t* pz = Zt + (4 * gq + rq) * SZ + nt * 16 + (cp ^ wsw(4 * gq));
-#pragma unroll
-      for (int s = 0; s < KSTEPS; ++s) {
-        const bfx8 af = join_tr(lds_tr16(pa + 32 * s * SA), lds_tr16(pa + (32 * s + 16) * SA));
-        const bfx8 bf = join_tr(lds_tr16(pz + 32 * s * SZ), lds_tr16(pz + (32 * s + 16) * SZ));
-        acc[i] = mfma16(af, bf, acc[i]);
-      }
-    }
-  }
-  const bool atomic = g.atomic != 0;
-  if (dob && (int)threadIdx.x < NB) {
-    const int nn = n_lo + threadIdx.x;
-    if (nn < g.N) {
-      float* pdb = nn < g.nsplit ? g.db + nn : g.db2 + (nn - g.nsplit);
-      const float s = dbs * kInvLossScale;
-      if (atomic) atomicAdd(pdb, s); else *pdb = s;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PERW; ++i) {
-    const int tile = wave + 4 * i;
-    const int kt = tile / NTt, nt = tile - kt * NTt;
-    const int n = n_lo + nt * 16 + (lane & 15);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = k_lo + kt * 16 + 4 * (lane >> 4) + q;
-      if (k < a.K && n < g.N) {
-        float* o = n < g.nsplit ? g.dw + (int64_t)k * g.nsplit + n
-                                : g.dw2 + (int64_t)k * (g.N - g.nsplit) + (n - g.nsplit);
-        const float v = acc[i][q] * (g.scale * kInvLossScale);
-        if (atomic) atomicAdd(o, v); else *o = v;
-      }
-    }
-  }
+  wgrad_block_sum<LD, MC, KB, NB>(a, g, bx, by, bz, lds, 1);
 }
 #endif
 
-
 // Multi-chunk variant (the low-rank DP member, L_DENSE_WGRAD_LR): ONE block per weight tile sums
 // g.mloop consecutive MC-row chunks in a fixed order, accumulators in registers, plain stores:
-// bit-identical on every rank that runs it on the same all-gathered rows. Staged like the
-// fp32 build's body ([k][m] / [n][m], m contiguous) for every element type; off the critical
-// path (a graph branch beside the dgrad chain), so simplicity over staging speed. g.db_zero:
-// store 0 into the bias gradient (ranks != 0: the caller's all-reduce then sums it once).
+// bit-identical on every rank that runs it on the same all-gathered rows. Off the critical path (a
+// graph branch beside the dgrad chain). g.db_zero: store 0 into the bias gradient (ranks != 0: the
+// caller's all-reduce then sums it once).
+// The ONE weight-gradient body not composed of wgrad_dev.h's tile parts: written from them it ran
+// 0.25 us (6 %) slower at mloop <= 2 (profiles/wgrad_parts.md), so it keeps its own text -- the stage's
+// layouts written out (fp32 build: transposed with rows of MC + 8, not WgradTile's MC + 4; 16-bit
+// builds: WgradTile's row-major layout). A change to the parts' loads, 16-bit staging or stores has
+// a second copy here.
 template <class LD, int MC, int KB, int NB>
 DQN_DEV void wgrad_block_multi(const ConvArgs& a, const WgradArgs& g, int by, int bz, act_t* lds) {
-  constexpr int LR = MC + 8;                     // [k][m] / [n][m] rows (every build: see WgradTile)
+  constexpr int LR = MC + 8;                     // fp32 build: [k][m] / [n][m] rows
   constexpr int SA = KB + 16, SZ = NB + 16;      // 16-bit builds: row-major [m][k] / [m][n] (see WgradTile)
   constexpr int TPR = 256 / MC;
   constexpr int GA = KB / 8 / TPR, GZ = NB / 8 / TPR;
@@ -1182,21 +1062,17 @@ constexpr int kLoadBatch(int u) { return DQN_ACT_F32 ? (u + 1) / 2 : u; }
   } while (0)
 #define IGEMM_LAUNCH(LD, MT, NT, WM, WN, KS, EPI) IGEMM_LAUNCH_U(LD, MT, NT, WM, WN, KS, EPI, 4)
 
-using NatC1 = ConvLoader<uint8_t, 4, 8, 8, 4>;
-using NatC2 = ConvLoader<act_t, 32, 4, 4, 2>;
-using NatC3 = ConvLoader<act_t, 64, 3, 3, 1>;
 using NatD3 = DgradLoader<64, 3, 3, 1>;
 using NatD2 = DgradLoader<64, 4, 4, 2>;
-using NatF1 = FrameLoader<8, 8, 4>;
 
 // layer kinds: see dqn_nets_k.h.  Tiles: (MT, NT, WM, WN, KSPLIT, EPI)
 int launch_igemm(int kind, const ConvArgs& a, int ninst, hipStream_t st) {
   switch (kind) {
     // ---- forward, fused bias + ReLU, bf16 NHWC out
-    case L_NAT_CONV1_FWD: IGEMM_LAUNCH(NatC1, 1, 2, 4, 1, 1, 0); return 0;       // K 256: 8 k-steps
-    case L_NAT_CONV1_FRAMES: IGEMM_LAUNCH(NatF1, 1, 2, 4, 1, 1, 0); return 0;
-    case L_NAT_CONV2_FWD: IGEMM_LAUNCH(NatC2, 1, 4, 2, 1, 2, 0); return 0;       // K 512: split-K 2
-    case L_NAT_CONV3_FWD: IGEMM_LAUNCH(NatC3, 1, 4, 2, 1, 2, 0); return 0;       // K 576: split-K 2
+    case L_NAT_CONV1_FWD: IGEMM_LAUNCH(WgC1, 1, 2, 4, 1, 1, 0); return 0;       // K 256: 8 k-steps
+    case L_NAT_CONV1_FRAMES: IGEMM_LAUNCH(WgF1, 1, 2, 4, 1, 1, 0); return 0;
+    case L_NAT_CONV2_FWD: IGEMM_LAUNCH(WgC2, 1, 4, 2, 1, 2, 0); return 0;       // K 512: split-K 2
+    case L_NAT_CONV3_FWD: IGEMM_LAUNCH(WgC3, 1, 4, 2, 1, 2, 0); return 0;       // K 576: split-K 2
     // K 3136 = 98 k-steps, split-K 8: one 13-step load batch per wave; 16-row blocks so the
     // B=32 step spreads over 2x the CUs (each block's L2->CU bytes are the bound, not MFMA)
     case L_DENSE_FWD_RELU:
@@ -1260,22 +1136,43 @@ int launch_dgrad_chain(const ConvArgs& a0, const ConvArgs& a1, const ConvArgs& a
   return 0;
 }
 
-#define WGRAD_LAUNCH(LD, MC, KB, NB)                                                                   \
-  do {                                                                                                 \
-    dim3 grid((a.M + MC - 1) / MC, (a.K + KB - 1) / KB, (g.N + NB - 1) / NB);                          \
-    WgradArgs gg = g;                                                                                  \
-    gg.atomic = grid.x > 1 ? 1 : 0;                                                                    \
-    hipLaunchKernelGGL((wgrad_kernel<LD, MC, KB, NB>), grid, dim3(256), 0, st, a, gg);                 \
-  } while (0)
+// The weight-gradient tiles of the per-layer and grouped launches, one row per (launcher, kind):
+//   L(kind, loader, MC, KB, NB)    launch_wgrad's tile
+//   GC(kind, loader, KB, NB)       a grouped conv member, in 128-row chunks (kind as is: the fp32 build,
+//                                  whose 256-row staging would not fit twice per CU, and the deterministic
+//                                  partial members) and 256-row chunks (kind + kGrpMC256: 80 KB, 2 blocks /
+//                                  CU, half the blocks and atomic partials: the 16-bit builds)
+//   G(kind, loader, MC, KB, NB)    a grouped dense member
+// (the low-rank member's 64 x 32 x 64 multi-chunk tile is launch_wgrad's own case)
+constexpr int kGrpMC256 = 0x40;
+#define DQN_WGRAD_TILES(L, GC, G)                                                          \
+  L(L_NAT_CONV1_FWD, WgC1, 128, 256, 32) /* 100 chunks (B=32) */                           \
+  L(L_NAT_CONV1_FRAMES, WgF1, 128, 256, 32)                                                \
+  L(L_NAT_CONV2_FWD, WgC2, 128, 128, 64) /* 21 x 4 blocks */                               \
+  L(L_NAT_CONV3_FWD, WgC3, 128, 192, 64) /* 13 x 3 blocks */                               \
+  L(L_DENSE_FWD_RELU, DenseLoader, 32, 64, 128)                                            \
+  L(L_HEAD_WGRAD, DenseLoader, 32, 64, 64)                                                 \
+  GC(L_NAT_CONV1_FWD, WgC1, 64, 32)                                                        \
+  GC(L_NAT_CONV1_FRAMES, WgF1, 64, 32)                                                     \
+  GC(L_NAT_CONV2_FWD, WgC2, 64, 64)                                                        \
+  GC(L_NAT_CONV3_FWD, WgC3, 64, 64)                                                        \
+  G(L_DENSE_FWD_RELU, DenseLoader, 32, 64, 128)                                            \
+  G(L_HEAD_WGRAD, DenseLoader, 32, 64, 64)
+#define DQN_NO_ROW(...)
+#define DQN_GC_ROWS(X, KIND, LD, KB, NB) X(KIND, LD, 128, KB, NB) X(KIND + kGrpMC256, LD, 256, KB, NB)
 
 int launch_wgrad(int kind, const ConvArgs& a, const WgradArgs& g, hipStream_t st) {
   switch (kind) {
-    case L_NAT_CONV1_FWD: WGRAD_LAUNCH(NatC1, 128, 256, 32); return 0;   // 100 chunks (B=32)
-    case L_NAT_CONV1_FRAMES: WGRAD_LAUNCH(NatF1, 128, 256, 32); return 0;
-    case L_NAT_CONV2_FWD: WGRAD_LAUNCH(NatC2, 128, 128, 64); return 0;   // 21 x 4 blocks
-    case L_NAT_CONV3_FWD: WGRAD_LAUNCH(NatC3, 128, 192, 64); return 0;   // 13 x 3 blocks
-    case L_DENSE_FWD_RELU: WGRAD_LAUNCH(DenseLoader, 32, 64, 128); return 0;
-    case L_HEAD_WGRAD: WGRAD_LAUNCH(DenseLoader, 32, 64, 64); return 0;
+#define DQN_L(KIND, LD, MC, KB, NB)                                                        \
+    case KIND: {                                                                           \
+      dim3 grid((a.M + MC - 1) / MC, (a.K + KB - 1) / KB, (g.N + NB - 1) / NB);            \
+      WgradArgs gg = g;                                                                    \
+      gg.atomic = grid.x > 1 ? 1 : 0;                                                      \
+      hipLaunchKernelGGL((wgrad_kernel<LD, MC, KB, NB>), grid, dim3(256), 0, st, a, gg);   \
+      return 0;                                                                            \
+    }
+    DQN_WGRAD_TILES(DQN_L, DQN_NO_ROW, DQN_NO_ROW)
+#undef DQN_L
     case L_DENSE_WGRAD_LR: {                     // ONE block per weight tile over all g.mloop 64-row chunks
       if (g.mloop < 1 || 64 * g.mloop < a.M) return -1;
       // tiles per block: 32 x 64 (784 blocks for Nature's fc; measured 11.0 vs 11.7 us for 64 x 128
@@ -1295,46 +1192,30 @@ namespace dqn {
 template <class LD, int MC, int KB, int NB>
 DQN_DEV void group_member(const ConvArgs& a, const WgradArgs& g, int b, int gx, int gy, act_t* lds) {
   const int bx = b % gx, r = b / gx, by = r % gy, bz = r / gy;
+  // deterministic partial members: 128-row conv chunks of the 16-bit builds (the fp32 build refuses them:
+  // launch_wgrad_group)
 #if DQN_ACT_F32
-  wgrad_block<LD, MC, KB, NB>(a, g, bx, by, bz, lds);
+  constexpr bool kPart = false;
 #else
   constexpr bool kPart = MC == 128 && !std::is_same<LD, DenseLoader>::value;
-  constexpr bool kMulti = kPart;
-  if constexpr (kMulti) {
-    if (g.part == nullptr && g.mloop > 1) {
-      // chunk group bx: mloop consecutive M-chunks summed in registers, ONE set of fp32 atomics
-      // per group (the atomic bytes of the member / mloop: they run at the memory side, ~1.3 TB/s
-      // chip-wide, the grouped launch's floor with one set per chunk)
+#endif
+  if constexpr (kPart) {
+    if (g.part != nullptr) {
+      // chunk group bx (mloop chunks) -> its partial slice ([K][N] weights, then [N] bias), as the
+      // member's own dW / db with no split (plain stores)
+      WgradArgs gp = g;
       const int nch = (a.M + MC - 1) / MC, c0 = bx * g.mloop;
-      wgrad_block_det<LD, MC, KB, NB>(a, g, c0, by, bz, lds, min(nch, c0 + g.mloop) - c0);
+      gp.dw = g.part + (int64_t)bx * g.pstride;
+      gp.db = gp.dw + (int64_t)a.K * g.N;
+      gp.nsplit = g.N;
+      gp.atomic = 0;
+      wgrad_block_sum<LD, MC, KB, NB>(a, gp, c0, by, bz, lds, min(nch, c0 + g.mloop) - c0);
       return;
     }
   }
-  if (!kPart || g.part == nullptr) {
-    wgrad_block<LD, MC, KB, NB>(a, g, bx, by, bz, lds);
-    return;
-  }
-  // deterministic: chunk group bx -> its partial slice ([K][N] weights, then [N] bias), as the
-  // member's own dW / db with no split (plain stores)
-  WgradArgs gp = g;
-  const int nch = (a.M + MC - 1) / MC, c0 = bx * g.mloop;
-  gp.dw = g.part + (int64_t)bx * g.pstride;
-  gp.db = gp.dw + (int64_t)a.K * g.N;
-  gp.nsplit = g.N;
-  gp.atomic = 0;
-  if constexpr (kPart) wgrad_block_det<LD, MC, KB, NB>(a, gp, c0, by, bz, lds, min(nch, c0 + g.mloop) - c0);
-#endif
+  wgrad_block<LD, MC, KB, NB>(a, g, bx, by, bz, lds);
 }
 
-// conv members' M-chunk: 128 rows (kind as is: the fp32 build, whose 256-row staging would not
-// fit twice per CU, and the deterministic partial members) or 256 rows (kind | kGrpMC256: 80 KB,
-// 2 blocks / CU, half the blocks and atomic partials: the 16-bit builds)
-constexpr int kGrpMC256 = 0x40;
-#define GRP_CONV_CASES(OFF, MC)                                                                                    \
-  case L_NAT_CONV1_FWD + OFF: group_member<NatC1, MC, 64, 32>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;    \
-  case L_NAT_CONV1_FRAMES + OFF: group_member<NatF1, MC, 64, 32>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break; \
-  case L_NAT_CONV2_FWD + OFF: group_member<NatC2, MC, 64, 64>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;    \
-  case L_NAT_CONV3_FWD + OFF: group_member<NatC3, MC, 64, 64>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;
 // (<= 128 VGPRs: 4 waves / SIMD, the 4 blocks / CU the conv members' LDS allows)
 // (fp32 build: 3 waves / EU -- at 4 the 128-VGPR cap spilled 20 B / lane to scratch)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQN_ACT_F32 ? 3 : 4))) wgrad_group_kernel(WgradGroup Gv) {
@@ -1347,34 +1228,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DQN_AC
   int b = blockIdx.x, i = 0;
   while (i < G.n - 1 && b >= G.nblk[i]) { b -= G.nblk[i]; ++i; }
   switch (G.kind[i]) {
-    GRP_CONV_CASES(0, 128)
-    GRP_CONV_CASES(kGrpMC256, 256)
-    case L_DENSE_FWD_RELU: group_member<DenseLoader, 32, 64, 128>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;
-    case L_HEAD_WGRAD: group_member<DenseLoader, 32, 64, 64>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;
+#define DQN_G(KIND, LD, MC, KB, NB) \
+    case KIND: group_member<LD, MC, KB, NB>(G.a[i], G.g[i], b, G.gx[i], G.gy[i], glds); break;
+#define DQN_GC(KIND, LD, KB, NB) DQN_GC_ROWS(DQN_G, KIND, LD, KB, NB)
+    DQN_WGRAD_TILES(DQN_NO_ROW, DQN_GC, DQN_G)
+#undef DQN_GC
+#undef DQN_G
     default: break;
   }
 }
-#undef GRP_CONV_CASES
 }  // namespace dqn
 
+// a grouped member's tile and its staging bytes
 static bool wgrad_tiles(int kind, int& MC, int& KB, int& NB, size_t& lds) {
   switch (kind) {
-    case L_NAT_CONV1_FWD: case L_NAT_CONV1_FRAMES: MC = 128; KB = 64; NB = 32; break;
-    case L_NAT_CONV2_FWD: MC = 128; KB = 64; NB = 64; break;
-    case L_NAT_CONV3_FWD: MC = 128; KB = 64; NB = 64; break;
-    case L_NAT_CONV1_FWD + kGrpMC256: case L_NAT_CONV1_FRAMES + kGrpMC256: MC = 256; KB = 64; NB = 32; break;
-    case L_NAT_CONV2_FWD + kGrpMC256: MC = 256; KB = 64; NB = 64; break;
-    case L_NAT_CONV3_FWD + kGrpMC256: MC = 256; KB = 64; NB = 64; break;
-    case L_DENSE_FWD_RELU: MC = 32; KB = 64; NB = 128; break;
-    case L_HEAD_WGRAD: MC = 32; KB = 64; NB = 64; break;
+#define DQN_G(KIND, LD, MC_, KB_, NB_) \
+    case KIND: MC = MC_; KB = KB_; NB = NB_; lds = WgradTile<MC_, KB_, NB_>::lds_bytes; return true;
+#define DQN_GC(KIND, LD, KB, NB) DQN_GC_ROWS(DQN_G, KIND, LD, KB, NB)
+    DQN_WGRAD_TILES(DQN_NO_ROW, DQN_GC, DQN_G)
+#undef DQN_GC
+#undef DQN_G
     default: return false;
   }
-#if DQN_ACT_F32
-  lds = (size_t)(KB + NB) * (MC + kF32Pad) * sizeof(act_t);   // WgradTile<...>::lds_bytes
-#else
-  lds = (size_t)MC * (KB + 16 + NB + 16) * sizeof(act_t);      // WgradTile<...>::lds_bytes
-#endif
-  return true;
 }
 
 int launch_wgrad_group(WgradGroup G, hipStream_t st) {

@@ -99,16 +99,22 @@ def test_deferred_fc_grad_matches_materialised(extra):
     assert torch.equal(a3['step'], b3['step'])
 
 
-@pytest.mark.parametrize('extra', ['', '--dueling --double_dqn --loss=huber', RAINBOW + ' --prioritized_replay',
-                                   '--optimizer=adam --prioritized_replay'])
-def test_split_update_matches_separate_wgrad(extra):
+_SPLIT_EXTRAS = ['', '--dueling --double_dqn --loss=huber', RAINBOW + ' --prioritized_replay',
+                 '--optimizer=adam --prioritized_replay']
+
+
+@pytest.mark.parametrize('extra,B', [pytest.param(e, 32, id=e) for e in _SPLIT_EXTRAS] +
+                         [pytest.param('', 3, id='B3'), pytest.param('', 5, id='B5')])
+def test_split_update_matches_separate_wgrad(extra, B):
     """Split update (``--fuse_wgrad_update=1``): the conv / output-layer weight gradients run in
     the leading blocks of the optimizer's first launch beside the fc update, the other tensors
     in a second launch -- vs the grouped weight-gradient launch before one optimizer launch.
-    Same math; the conv gradients' fp32 atomics sum 256-row chunk groups in another order."""
+    Same math; the conv gradients' fp32 atomics sum 256-row chunk groups in another order.
+    B = 3 and 5 (plain net): the fused tile's short last chunk groups -- conv3's 147 / 245 rows are
+    2 chunks of 128 (one group), conv1's 1200 / 2000 rows end in a partly filled chunk."""
     runs = []
     for fw in (1, 0):
-        net, learner = _learner(extra + ' --fuse_wgrad_update=%d' % fw, True)
+        net, learner = _learner(extra + ' --fuse_wgrad_update=%d' % fw, True, B=B)
         assert learner._defer_wgrad == bool(fw)
         learner.step()
         torch.cuda.synchronize()
