@@ -103,7 +103,7 @@ struct ActorArgs {
 
 struct HeadArgs {
   int B, A, HID, dueling, huber, infer;
-  float delta;
+  float delta;                   // Huber threshold: the scalar heads' delta (huber != 0); the QR-DQN head's kappa
   const void* h[3];
   const void* pw[3];         // packed bf16 head fragments (plain output / advantage), [HID/32][N16][64][8]
   const void* pwv[3];        // packed value-head fragments (dueling, N = 1)
@@ -119,7 +119,8 @@ struct HeadArgs {
   ActorArgs actor;
   const void* act_h;             // training mode + fused acting: the actors' hidden layer [E][HH]
   int act_E;                     //   (an extra workgroup runs the acting step), 0 = off
-  int atoms;                     // C51 head (rainbow.hip): atoms per action, support [vmin, vmax]
+  int atoms;                     // C51 head (rainbow.hip): atoms per action, support [vmin, vmax];
+                                 // QR-DQN head (qr_head.hip): quantiles per action, kappa in delta
   float vmin, vmax;
   int64_t* prof;                 // optional s_memtime phase stamps of block 0 (profiling)
   const float* lgi[3];           // C51: precomputed logits rows [B][KD] per instance (one igemm over the
@@ -285,6 +286,10 @@ void launch_trunk_fwd(const dqn::TrunkArgs& a, int B, int ninst, hipStream_t st)
 void launch_c51_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t c51_head_lds_bytes(const dqn::HeadArgs& a);
 int c51_train_blocks(const dqn::HeadArgs& a);     // learner blocks = loss partials of the training head
+// QR-DQN head (qr_head.hip): HeadArgs::atoms = quantiles per action, HeadArgs::delta = kappa
+void launch_qr_head(const dqn::HeadArgs& a, hipStream_t st);
+size_t qr_head_lds_bytes(const dqn::HeadArgs& a);
+int qr_train_blocks(const dqn::HeadArgs& a);
 void launch_noisy_mix(const float* flat, float* eff, const float* noise, const dqn::NoisyJob* jobs, int njobs,
                       int max_elems, hipStream_t st);
 void launch_noisy_grad(float* grad, const float* noise, const dqn::NoisyJob* jobs, int njobs, int max_elems,

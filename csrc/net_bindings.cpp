@@ -404,6 +404,38 @@ void c51_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<
   launch_c51_head(a, cur_stream());
 }
 
+// QR-DQN head (qr_head.hip): the arguments of c51_head with dist = [quantiles], flts = [kappa];
+// lg = the instances' quantile rows (the same combined output layer and row layout)
+void qr_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<double> flts, std::vector<int64_t> h,
+             std::vector<int64_t> w, std::vector<int64_t> b, std::vector<int64_t> wv, std::vector<int64_t> bv,
+             std::vector<int64_t> io, std::vector<int64_t> pw, std::vector<int64_t> pwv, std::vector<int64_t> zero,
+             std::vector<int64_t> actor, std::vector<double> actor_f, std::vector<int64_t> lg, int64_t act_h,
+             std::vector<int64_t> qp) {
+  TORCH_CHECK(dist.size() == 1 && flts.size() == 1, "qr args");
+  dqn::HeadArgs a = head_args(ints, h, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h);
+  a.atoms = (int)dist[0]; a.delta = (float)flts[0];
+  TORCH_CHECK(a.atoms >= 2 && a.atoms <= 64, "QR-DQN: 2..64 quantiles (one wave64 lane per quantile)");
+  TORCH_CHECK(a.delta > 0.f, "QR-DQN: kappa > 0");
+  TORCH_CHECK(qr_head_lds_bytes(a) <= 160 * 1024, "QR head: batch too large for one workgroup's LDS");
+  if (!a.infer) {
+    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, "QR training: loss partials, dout16, prio");
+    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0, "QR training: actions, rewards, dones, gammas");
+    a.loss_parts = P<float*>(qp[0]);
+    a.dq16 = P<void*>(qp[1]);
+  }
+  if (a.act_E > 0) {
+    TORCH_CHECK(!lg.empty(), "qr fused acting: the actors' quantile rows");
+    a.act_lgi = P<const float*>(lg.back());
+    lg.pop_back();
+  }
+  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 2 || lg.size() == 3), "qr: quantile rows of every instance");
+  for (size_t i = 0; i < lg.size(); ++i) {
+    TORCH_CHECK(lg[i] != 0, "qr: null quantile rows");
+    a.lgi[i] = P<const float*>(lg[i]);
+  }
+  launch_qr_head(a, cur_stream());
+}
+
 void noisy_mix(int64_t flat, int64_t eff, int64_t noise, int64_t jobs, int64_t njobs, int64_t max_elems) {
   launch_noisy_mix(P<const float*>(flat), P<float*>(eff), P<const float*>(noise), P<const dqn::NoisyJob*>(jobs),
                    (int)njobs, (int)max_elems, cur_stream());
@@ -495,6 +527,11 @@ void register_net_ops(pybind11::module_& m) {
         pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
         pybind11::arg("actor_f"), pybind11::arg("prof") = 0, pybind11::arg("lg") = std::vector<int64_t>{},
         pybind11::arg("act_h") = 0, pybind11::arg("qp") = std::vector<int64_t>{});
+  m.def("qnet_qr_head", &qr_head, pybind11::arg("ints"), pybind11::arg("dist"), pybind11::arg("flts"),
+        pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("b"), pybind11::arg("wv"), pybind11::arg("bv"),
+        pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
+        pybind11::arg("actor_f"), pybind11::arg("lg") = std::vector<int64_t>{}, pybind11::arg("act_h") = 0,
+        pybind11::arg("qp") = std::vector<int64_t>{});
   m.def("qnet_noisy_mix", &noisy_mix);
   m.def("qnet_noisy_grad", &noisy_grad);
   m.attr("NOISY_JOB_INTS") = (int)(sizeof(dqn::NoisyJob) / sizeof(int));

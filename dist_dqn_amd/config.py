@@ -120,6 +120,9 @@ def build_parser() -> argparse.ArgumentParser:
     a('--num_atoms', default=51, type=int)
     a('--v_min', default=-10.0, type=float)
     a('--v_max', default=10.0, type=float)
+    a('--quantile', action='store_true', help='QR-DQN head (quantile regression; no --v_min/--v_max support)')
+    a('--num_quantiles', default=32, type=int, help='QR-DQN quantiles per action (HIP executor: 2..64)')
+    a('--qr_kappa', default=1.0, type=float, help='QR-DQN Huber threshold kappa (> 0)')
     a('--noisy', action='store_true', help='Factorised-Gaussian noisy FC layers')
     a('--noisy_sigma0', default=0.5, type=float)
     a('--target_update_tau', default=1.0, type=float,
@@ -283,6 +286,9 @@ class Config:
     num_atoms: int = 51
     v_min: float = -10.0
     v_max: float = 10.0
+    quantile: bool = False
+    num_quantiles: int = 32
+    qr_kappa: float = 1.0
     noisy: bool = False
     noisy_sigma0: float = 0.5
     target_update_tau: float = 1.0
@@ -344,7 +350,16 @@ class Config:
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> Config:
-    return Config.from_namespace(build_parser().parse_args(argv))
+    p = build_parser()
+    ns = p.parse_args(argv)
+    if ns.quantile:
+        if ns.distributional:
+            p.error('--quantile and --distributional select different distributional heads: give one')
+        if ns.num_quantiles < 2:
+            p.error('--num_quantiles must be at least 2 (the HIP executor takes 2..64), got %d' % ns.num_quantiles)
+        if not ns.qr_kappa > 0.0:
+            p.error('--qr_kappa must be > 0 (the Huber threshold of the quantile loss), got %g' % ns.qr_kappa)
+    return Config.from_namespace(ns)
 
 
 def preset(env_type: str, env_name: str, extra: str = '') -> Config:

@@ -12,7 +12,7 @@ Extension:
   * ``nature`` — Mnih et al. 2015: VALID convs 32x8x8/4, 64x4x4/2, 64x3x3/1,
     no pooling, FC512 ReLU -> A.
 Heads (any network): plain, dueling (V + A - mean A), distributional (C51
-atoms), noisy FC layers (factorised Gaussian).
+atoms or QR-DQN quantiles), noisy FC layers (factorised Gaussian).
 
 Parameter names are the TF variable names of the reference
 (`conv1/w` ..., `output/b`) so the checkpoint layout round-trips; weight
@@ -81,6 +81,8 @@ class ArchSpec:
     v_max: float = 10.0
     noisy: bool = False
     noisy_sigma0: float = 0.5
+    quantile: bool = False            # QR-DQN: the `atoms` outputs per action are quantiles (no support)
+    kappa: float = 1.0                # QR-DQN Huber threshold
 
     @property
     def dueling(self) -> bool:
@@ -161,9 +163,20 @@ def _conv_stack(input_shape, layers, padding, pool) -> Tuple[ConvSpec, ...]:
 def build_arch(network: str, input_shape: Sequence[int], num_actions: int, *,
                dueling: bool = False, distributional: bool = False, num_atoms: int = 51,
                v_min: float = -10.0, v_max: float = 10.0, noisy: bool = False,
-               noisy_sigma0: float = 0.5) -> ArchSpec:
+               noisy_sigma0: float = 0.5, quantile: bool = False, num_quantiles: int = 32,
+               kappa: float = 1.0) -> ArchSpec:
     input_shape = tuple(int(x) for x in input_shape)
-    atoms = num_atoms if distributional else 1
+    if quantile:
+        # QR-DQN: num_quantiles outputs per action where C51 has num_atoms, so every width derived
+        # from `atoms` (layers, packed fragments, checkpoint tensors) is C51's for the same count
+        if distributional:
+            raise RuntimeError('quantile and distributional are different heads: choose one')
+        if num_quantiles < 2:
+            raise RuntimeError('QR-DQN needs at least 2 quantiles, got %d' % num_quantiles)
+        if not kappa > 0.0:
+            raise RuntimeError('QR-DQN Huber threshold kappa must be > 0, got %g' % kappa)
+    atoms = num_quantiles if quantile else num_atoms if distributional else 1
+    qr = (bool(quantile), float(kappa))
     A = num_actions
     if network == 'simple':
         if len(input_shape) != 1:
@@ -176,7 +189,7 @@ def build_arch(network: str, input_shape: Sequence[int], num_actions: int, *,
         else:
             value = ()
             head = (DenseSpec('output', 20, A * atoms, None, noisy=noisy),)
-        return ArchSpec(network, input_shape, A, (), trunk, head, value, atoms, v_min, v_max, noisy, noisy_sigma0)
+        return ArchSpec(network, input_shape, A, (), trunk, head, value, atoms, v_min, v_max, noisy, noisy_sigma0, *qr)
 
     if len(input_shape) != 3:
         raise RuntimeError('%s expects 3-d input (H, W, frames)' % network)
@@ -205,11 +218,12 @@ def build_arch(network: str, input_shape: Sequence[int], num_actions: int, *,
         value = ()
         head = (DenseSpec('fcl', flat, hidden, 'relu', noisy=noisy),
                 DenseSpec('output', hidden, A * atoms, None, noisy=noisy))
-    return ArchSpec(network, input_shape, A, convs, (), head, value, atoms, v_min, v_max, noisy, noisy_sigma0)
+    return ArchSpec(network, input_shape, A, convs, (), head, value, atoms, v_min, v_max, noisy, noisy_sigma0, *qr)
 
 
 def arch_from_config(config, input_shape, num_actions) -> ArchSpec:
     return build_arch(config.network, input_shape, num_actions,
                       dueling=config.dueling, distributional=config.distributional,
                       num_atoms=config.num_atoms, v_min=config.v_min, v_max=config.v_max,
-                      noisy=config.noisy, noisy_sigma0=config.noisy_sigma0)
+                      noisy=config.noisy, noisy_sigma0=config.noisy_sigma0,
+                      quantile=config.quantile, num_quantiles=config.num_quantiles, kappa=config.qr_kappa)

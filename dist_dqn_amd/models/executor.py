@@ -34,12 +34,12 @@ class TorchExecutor:
             return torch_net.forward(self.arch, flat, self.layout, x, self.input_scale, noise)
 
     def q_values(self, flat, x, noise=None):
-        return torch_net.q_from_logits(self.arch, self.forward(flat, x, noise))
+        return torch_net.q_from_output(self.arch, self.forward(flat, x, noise))
 
     def loss_and_grad(self, online: torch.Tensor, target: torch.Tensor, batch: Dict[str, torch.Tensor],
                       grad_out: torch.Tensor, noise: Optional[torch.Tensor] = None,
                       noise_target: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Writes dLoss/dflat into grad_out; returns (loss [1], |td| or CE per sample [B])."""
+        """Writes dLoss/dflat into grad_out; returns (loss [1], |td|, CE or quantile loss per sample [B])."""
         arch = self.arch
         flat = online.detach().requires_grad_(True)
         out = torch_net.forward(arch, flat, self.layout, batch['states'], self.input_scale, noise)
@@ -50,7 +50,8 @@ class TorchExecutor:
         from ..ops.td import td_loss
         loss, prio = td_loss(out, batch['actions'], batch['rewards'], batch['dones'], batch['gammas'], nt, no,
                              batch.get('weights'), self.loss_kind, self.delta, arch.distributional,
-                             arch.v_min, arch.v_max, pure_torch=self.oracle)
+                             arch.v_min, arch.v_max, pure_torch=self.oracle,
+                             kappa=arch.kappa if arch.quantile else None)
         g, = torch.autograd.grad(loss, flat)
         grad_out.copy_(g)
         return loss.detach().view(1), prio

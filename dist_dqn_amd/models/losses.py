@@ -5,9 +5,10 @@ the host at `/root/reference/src/dqn_agent.py:224-253`):
     y  = r + gamma * max_a' Q_target(s', a')   (y = r when terminal)
     L  = mean((Q(s, a) - y)^2) + reg_param * sum_w 0.5 ||w||^2
 Extensions: Huber, Double DQN (argmax by the online net), n-step discount
-(gamma_n = gamma ** n), importance weights (PER), and the C51 categorical
-projection loss. The L2 term is NOT part of these functions: it is applied
-as ``grad += reg_param * w`` in the optimizer (same gradient, no extra pass).
+(gamma_n = gamma ** n), importance weights (PER), the C51 categorical
+projection loss and the QR-DQN quantile regression loss. The L2 term is NOT
+part of these functions: it is applied as ``grad += reg_param * w`` in the
+optimizer (same gradient, no extra pass).
 """
 from __future__ import annotations
 
@@ -85,6 +86,34 @@ def c51_loss(logits: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor,
         m = categorical_projection(p_next, rewards, dones, gamma, v_min, v_max)
     logp = F.log_softmax(logits.float(), dim=-1)[torch.arange(B, device=logits.device), actions.long()]
     per = -(m * logp).sum(-1)
+    pr = per.detach().clone()
+    if weights is not None:
+        per = per * weights
+    return per.mean(), pr
+
+
+def qr_loss(theta: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor,
+            theta_next_target: torch.Tensor, theta_next_online: Optional[torch.Tensor], gamma, kappa: float,
+            weights: Optional[torch.Tensor] = None):
+    """Quantile regression loss (QR-DQN, Dabney et al. 2018). theta: [B, A, N] quantile values at
+    the midpoints tau_i = (2i + 1) / 2N. gamma: float or per-row [B] / [B, 1]. Returns (loss,
+    per-sample loss before the importance weights: the PER priority).
+
+    a* = argmax_a mean_j theta_sel(s', a)_j (first maximum; sel = online net under Double DQN),
+    u_ij = r + gamma (1 - done) theta_target(s', a*)_j - theta(s, a)_i,
+    per = sum_i mean_j |tau_i - 1{u_ij < 0}| L_kappa(u_ij) / kappa (L_kappa: Huber)."""
+    B, A, N = theta.shape
+    rows = torch.arange(B, device=theta.device)
+    with torch.no_grad():
+        sel = theta_next_online if theta_next_online is not None else theta_next_target
+        a_star = sel.float().mean(-1).argmax(dim=1)
+        g = torch.as_tensor(gamma, dtype=torch.float32, device=theta.device).reshape(-1, 1)
+        tz = rewards.float().view(B, 1) + g * (1.0 - dones.float().view(B, 1)) * theta_next_target.float()[rows, a_star]
+        tau = (2.0 * torch.arange(N, device=theta.device, dtype=torch.float32) + 1.0) / (2.0 * N)
+    th = theta.float()[rows, actions.long()]                       # [B, N]
+    u = tz.view(B, 1, N) - th.view(B, N, 1)                         # [B, i, j]
+    rho = (tau.view(1, N, 1) - (u.detach() < 0).float()).abs() * elementwise(u, 'huber', kappa) / kappa
+    per = rho.mean(2).sum(1)
     pr = per.detach().clone()
     if weights is not None:
         per = per * weights

@@ -71,7 +71,7 @@ def _dense(x, p, d: DenseSpec, noise: Optional[torch.Tensor], noff: int):
 
 def forward(arch: ArchSpec, flat: torch.Tensor, layout: FlatLayout, x: torch.Tensor,
             input_scale: float = 1.0, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Returns Q [B, A] (scalar heads) or logits [B, A, atoms] (distributional)."""
+    """Returns Q [B, A] (scalar heads), logits [B, A, atoms] (C51) or quantiles [B, A, N] (QR-DQN)."""
     p = unflatten(flat, layout)
     h = x.to(torch.float32)
     if input_scale != 1.0:
@@ -119,11 +119,17 @@ def reg_loss(layout: FlatLayout, flat: torch.Tensor) -> torch.Tensor:
     return 0.5 * (flat[:layout.reg_end].float() ** 2).sum()
 
 
-def q_from_logits(arch: ArchSpec, out: torch.Tensor) -> torch.Tensor:
+def q_from_output(arch: ArchSpec, out: torch.Tensor) -> torch.Tensor:
+    """Q [B, A] of ``forward``'s output: itself, the C51 expectation, or the mean over quantiles."""
     if not arch.distributional:
         return out
+    if arch.quantile:
+        return out.float().mean(-1)
     z = torch.linspace(arch.v_min, arch.v_max, arch.atoms, device=out.device)
     return (torch.softmax(out.float(), dim=-1) * z).sum(-1)
+
+
+q_from_logits = q_from_output
 
 
 def support(arch: ArchSpec, device) -> torch.Tensor:
@@ -137,4 +143,4 @@ def sample_noise(arch: ArchSpec, device, generator=None) -> Optional[torch.Tenso
     return torch.randn(n, device=device, generator=generator)
 
 
-__all__ = ['forward', 'reg_loss', 'q_from_logits', 'noise_size', 'sample_noise', 'support', 'math']
+__all__ = ['forward', 'reg_loss', 'q_from_logits', 'q_from_output', 'noise_size', 'sample_noise', 'support', 'math']

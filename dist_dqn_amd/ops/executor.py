@@ -12,7 +12,8 @@ buffer into bf16 MFMA B-fragments once per optimizer step (`repack`), and the
 target's packed copy is refreshed by a predicated copy when the target syncs.
 
 Supported: `nature` convs (84x84x4 uint8 frames), plain or dueling heads,
-scalar (MSE/Huber) or C51 distributional (csrc/kernels/rainbow.hip), noisy
+scalar (MSE/Huber), C51 distributional (csrc/kernels/rainbow.hip) or QR-DQN
+quantile (csrc/kernels/qr_head.hip; it shares every C51 buffer and launch but the head), noisy
 dense layers (factorised Gaussian: effective weights mixed on the GPU, then
 packed; sigma gradients split from the mu gradients), Double DQN, PER weights.
 The reference `cnn` (SAME convs + max-pools) runs on the per-sample fused
@@ -35,7 +36,7 @@ _KIND = dict(C1=1, C2=2, C3=3, DFWD=4, DF32=5, DDGRAD=6, D3=7, D2=8, F1=9, HW=11
 def supports(arch) -> bool:
     if arch.network not in ('nature', 'cnn'):
         return False
-    if arch.distributional and arch.atoms > 64:     # one wave64 lane per atom
+    if arch.distributional and arch.atoms > 64:     # one wave64 lane per atom (C51) / quantile (QR-DQN)
         return False
     if tuple(arch.input_shape) != (84, 84, 4):
         return False
@@ -130,6 +131,7 @@ class HipExecutor:
         self.dueling = arch.dueling
         self.dist = arch.distributional
         self.atoms = arch.atoms if self.dist else 1
+        self.quantile = arch.quantile     # QR-DQN: atoms = quantiles, no support
         self.NO = self.A * self.atoms          # output-layer width (advantage / plain head)
         self.noisy = arch.noisy
         self._eff: Dict[int, torch.Tensor] = {}
@@ -1070,7 +1072,7 @@ class HipExecutor:
         return ws
 
     def _head(self, ints, hs, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h=0, ws=None):
-        """Output layer + loss (+ backward) launch: scalar head or the C51 head."""
+        """Output layer + loss (+ backward) launch: scalar head, or the C51 / QR-DQN head."""
         if self.dist:
             B, dev = ints[0], ws['dq16'].device
             # (pw, pwv = the combined output layer's fragments and bias rows, see _head_packs)
@@ -1081,6 +1083,12 @@ class HipExecutor:
             else:
                 lg = self._c51_logits(hs, pw, pwv, B, dev)
             qp = [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()] if not ints[5] else []
+            if self.quantile:
+                if self.head_prof is not None:
+                    raise RuntimeError('head_prof: the QR-DQN head writes no phase stamps (C51 and scalar heads do)')
+                self.ext.qnet_qr_head(ints, [self.atoms], [float(self.arch.kappa)], hs, w, b, wv, bv, io, [], [],
+                                      zero, actor, actor_f, lg, act_h, qp)
+                return
             prof = self.head_prof.data_ptr() if self.head_prof is not None and not ints[5] else 0
             self.ext.qnet_c51_head(ints, [self.atoms], [float(self.arch.v_min), float(self.arch.v_max)], hs, w, b,
                                    wv, bv, io, [], [], zero, actor, actor_f, prof, lg, act_h, qp)
@@ -1090,7 +1098,7 @@ class HipExecutor:
                                     [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()], actor, actor_f, act_h, prof)
 
     def q_values(self, flat: torch.Tensor, x: torch.Tensor, noise=None) -> torch.Tensor:
-        """Q [B, A] (C51: expected value of the return distribution)."""
+        """Q [B, A] (C51: expected value of the return distribution; QR-DQN: mean of the quantiles)."""
         x = x.contiguous()
         self._check_states(x)
         B = x.shape[0]

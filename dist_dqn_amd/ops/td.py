@@ -42,9 +42,14 @@ class _TDLossHip(torch.autograd.Function):
 
 def td_loss(out: torch.Tensor, actions, rewards, dones, gammas, next_t, next_o=None,
             weights: Optional[torch.Tensor] = None, kind: str = 'mse', delta: float = 1.0,
-            distributional: bool = False, v_min: float = -10.0, v_max: float = 10.0, pure_torch: bool = False):
+            distributional: bool = False, v_min: float = -10.0, v_max: float = 10.0, pure_torch: bool = False,
+            kappa: Optional[float] = None):
     """Returns (mean loss [scalar], per-sample priority [B]). pure_torch: the torch oracle on any
-    device (the numerics reference of the HIP kernels)."""
+    device (the numerics reference of the HIP kernels). kappa: ``out`` holds QR-DQN quantiles
+    [B, A, N]; the quantile loss is the torch function on every device (the HIP training head
+    of the conv executor is csrc/kernels/qr_head.hip)."""
+    if kappa is not None:
+        return losses.qr_loss(out, actions, rewards, dones, next_t, next_o, gammas, kappa, weights)
     if out.is_cuda and not pure_torch:
         loss, prio = _TDLossHip.apply(out, actions, rewards, dones, gammas, next_t, next_o, weights, kind, delta,
                                       distributional, v_min, v_max)
