@@ -134,6 +134,10 @@ struct HeadArgs {
   // of the dH igemm and the dZ of the output layer's weight-gradient members
   float* loss_parts;
   void* dq16;
+  // Munchausen-DQN head (mdqn_head.hip; every other kernel ignores these): bonus weight alpha,
+  // softmax temperature tau (> 0) and the lower clip l0 (< 0) of tau * log pi. lgi = the scalar
+  // output rows [B][KD] of online(s), target(s'), target(s): Q / advantages in [0, A), dueling value at 32
+  float m_alpha, m_tau, m_clip;
 };
 
 // Fused fc forward + scalar head (fc_head.hip): the output layer is folded into the fc launch's
@@ -290,6 +294,10 @@ int c51_train_blocks(const dqn::HeadArgs& a);     // learner blocks = loss parti
 void launch_qr_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t qr_head_lds_bytes(const dqn::HeadArgs& a);
 int qr_train_blocks(const dqn::HeadArgs& a);
+// Munchausen-DQN head (mdqn_head.hip): HeadArgs::m_alpha / m_tau / m_clip, Huber threshold in delta
+void launch_mdqn_head(const dqn::HeadArgs& a, hipStream_t st);
+size_t mdqn_head_lds_bytes(const dqn::HeadArgs& a);
+int mdqn_train_blocks(const dqn::HeadArgs& a);
 void launch_noisy_mix(const float* flat, float* eff, const float* noise, const dqn::NoisyJob* jobs, int njobs,
                       int max_elems, hipStream_t st);
 void launch_noisy_grad(float* grad, const float* noise, const dqn::NoisyJob* jobs, int njobs, int max_elems,

@@ -133,6 +133,20 @@ DQN_DEV float wave_max_dpp(float v) {
                fmaxf(__int_as_float(__builtin_amdgcn_readlane(iv, 32)), __int_as_float(__builtin_amdgcn_readlane(iv, 48))));
 }
 
+// Half-wave reductions: lanes [0, 32) and lanes [32, 64) reduced separately, both results in
+// every lane (DPP row ops, then the two row totals of each half via readlane). All 64 lanes active.
+struct Half2 { float lo, hi; };
+DQN_DEV Half2 half_sum_dpp(float v) {
+  const int iv = __float_as_int(row16_sum(v));
+  return {__int_as_float(__builtin_amdgcn_readlane(iv, 0)) + __int_as_float(__builtin_amdgcn_readlane(iv, 16)),
+          __int_as_float(__builtin_amdgcn_readlane(iv, 32)) + __int_as_float(__builtin_amdgcn_readlane(iv, 48))};
+}
+DQN_DEV Half2 half_max_dpp(float v) {
+  const int iv = __float_as_int(row16_max(v));
+  return {fmaxf(__int_as_float(__builtin_amdgcn_readlane(iv, 0)), __int_as_float(__builtin_amdgcn_readlane(iv, 16))),
+          fmaxf(__int_as_float(__builtin_amdgcn_readlane(iv, 32)), __int_as_float(__builtin_amdgcn_readlane(iv, 48)))};
+}
+
 // -------------------------------------------------------------------- bf16
 DQN_DEV uint16_t f2bf(float f) {  // round-to-nearest-even (NaN kept by the cast path)
   __hip_bfloat16 b = __float2bfloat16(f);

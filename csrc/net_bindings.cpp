@@ -436,6 +436,45 @@ void qr_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<d
   launch_qr_head(a, cur_stream());
 }
 
+// Munchausen-DQN head (mdqn_head.hip): the arguments of qr_head with dist = [1] (one output per
+// action), flts = [alpha, tau, clip, huber_delta]; lg = the scalar output rows of online(s),
+// target(s'), target(s) (training) or of the one acting / q_values instance
+void mdqn_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<double> flts, std::vector<int64_t> h,
+               std::vector<int64_t> w, std::vector<int64_t> b, std::vector<int64_t> wv, std::vector<int64_t> bv,
+               std::vector<int64_t> io, std::vector<int64_t> pw, std::vector<int64_t> pwv, std::vector<int64_t> zero,
+               std::vector<int64_t> actor, std::vector<double> actor_f, std::vector<int64_t> lg, int64_t act_h,
+               std::vector<int64_t> qp) {
+  TORCH_CHECK(dist.size() == 1 && dist[0] == 1 && flts.size() == 4, "mdqn args");
+  TORCH_CHECK(ints.size() == 6 && ints[1] >= 1 && ints[1] <= 32,
+              "Munchausen head: 1..32 actions (one half-wave lane per action), got A = ", ints.size() == 6 ? ints[1] : -1);
+  dqn::HeadArgs a = head_args(ints, h, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h);
+  a.m_alpha = (float)flts[0]; a.m_tau = (float)flts[1]; a.m_clip = (float)flts[2]; a.delta = (float)flts[3];
+  TORCH_CHECK(a.m_alpha >= 0.f && a.m_alpha <= 1.f, "Munchausen head: 0 <= alpha <= 1");
+  TORCH_CHECK(a.m_tau > 0.f, "Munchausen head: tau > 0");
+  TORCH_CHECK(a.m_clip < 0.f, "Munchausen head: clip < 0");
+  TORCH_CHECK(!a.huber || a.delta > 0.f, "Munchausen head: Huber delta > 0");
+  TORCH_CHECK(mdqn_head_lds_bytes(a) <= 160 * 1024, "Munchausen head: batch too large for one workgroup's LDS");
+  if (!a.infer) {
+    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0,
+                "Munchausen training: loss partials, dout16, prio");
+    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0,
+                "Munchausen training: actions, rewards, dones, gammas");
+    a.loss_parts = P<float*>(qp[0]);
+    a.dq16 = P<void*>(qp[1]);
+  }
+  if (a.act_E > 0) {
+    TORCH_CHECK(!lg.empty(), "mdqn fused acting: the actors' output rows");
+    a.act_lgi = P<const float*>(lg.back());
+    lg.pop_back();
+  }
+  TORCH_CHECK(lg.size() == (a.infer ? 1u : 3u), "mdqn: output rows of every instance (online(s), target(s'), target(s))");
+  for (size_t i = 0; i < lg.size(); ++i) {
+    TORCH_CHECK(lg[i] != 0, "mdqn: null output rows");
+    a.lgi[i] = P<const float*>(lg[i]);
+  }
+  launch_mdqn_head(a, cur_stream());
+}
+
 void noisy_mix(int64_t flat, int64_t eff, int64_t noise, int64_t jobs, int64_t njobs, int64_t max_elems) {
   launch_noisy_mix(P<const float*>(flat), P<float*>(eff), P<const float*>(noise), P<const dqn::NoisyJob*>(jobs),
                    (int)njobs, (int)max_elems, cur_stream());
@@ -528,6 +567,11 @@ void register_net_ops(pybind11::module_& m) {
         pybind11::arg("actor_f"), pybind11::arg("prof") = 0, pybind11::arg("lg") = std::vector<int64_t>{},
         pybind11::arg("act_h") = 0, pybind11::arg("qp") = std::vector<int64_t>{});
   m.def("qnet_qr_head", &qr_head, pybind11::arg("ints"), pybind11::arg("dist"), pybind11::arg("flts"),
+        pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("b"), pybind11::arg("wv"), pybind11::arg("bv"),
+        pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
+        pybind11::arg("actor_f"), pybind11::arg("lg") = std::vector<int64_t>{}, pybind11::arg("act_h") = 0,
+        pybind11::arg("qp") = std::vector<int64_t>{});
+  m.def("qnet_mdqn_head", &mdqn_head, pybind11::arg("ints"), pybind11::arg("dist"), pybind11::arg("flts"),
         pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("b"), pybind11::arg("wv"), pybind11::arg("bv"),
         pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
         pybind11::arg("actor_f"), pybind11::arg("lg") = std::vector<int64_t>{}, pybind11::arg("act_h") = 0,

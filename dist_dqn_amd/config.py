@@ -123,6 +123,12 @@ def build_parser() -> argparse.ArgumentParser:
     a('--quantile', action='store_true', help='QR-DQN head (quantile regression; no --v_min/--v_max support)')
     a('--num_quantiles', default=32, type=int, help='QR-DQN quantiles per action (HIP executor: 2..64)')
     a('--qr_kappa', default=1.0, type=float, help='QR-DQN Huber threshold kappa (> 0)')
+    a('--munchausen', action='store_true',
+      help='Munchausen-DQN target (Vieillard et al. 2020): soft next-state value + alpha * clipped tau * log pi(a|s) '
+           'bonus of the sampled (s, a); scalar Q-network, no argmax')
+    a('--m_alpha', default=0.9, type=float, help='Munchausen bonus weight alpha (0 <= alpha <= 1)')
+    a('--m_tau', default=0.03, type=float, help='Munchausen softmax temperature tau (> 0)')
+    a('--m_clip', default=-1.0, type=float, help='Munchausen lower clip l0 of tau * log pi (< 0)')
     a('--noisy', action='store_true', help='Factorised-Gaussian noisy FC layers')
     a('--noisy_sigma0', default=0.5, type=float)
     a('--target_update_tau', default=1.0, type=float,
@@ -289,6 +295,10 @@ class Config:
     quantile: bool = False
     num_quantiles: int = 32
     qr_kappa: float = 1.0
+    munchausen: bool = False
+    m_alpha: float = 0.9
+    m_tau: float = 0.03
+    m_clip: float = -1.0
     noisy: bool = False
     noisy_sigma0: float = 0.5
     target_update_tau: float = 1.0
@@ -359,6 +369,21 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> Config:
             p.error('--num_quantiles must be at least 2 (the HIP executor takes 2..64), got %d' % ns.num_quantiles)
         if not ns.qr_kappa > 0.0:
             p.error('--qr_kappa must be > 0 (the Huber threshold of the quantile loss), got %g' % ns.qr_kappa)
+    if ns.munchausen:
+        for flag in ('distributional', 'quantile', 'double_dqn'):
+            if getattr(ns, flag):
+                p.error('--munchausen and --%s cannot be combined: the Munchausen target is a softmax over the '
+                        'target net\'s scalar Q values (no return distribution, no argmax to decouple)' % flag)
+        if ns.fuse_sampling == 1:
+            p.error('--munchausen and --fuse_sampling=1 cannot be combined: the trunk\'s in-kernel sampling reads '
+                    'next-state slots for every instance after the first, and the Munchausen step runs the target '
+                    'on the sampled states too (use --fuse_sampling=2, the default, or 0)')
+        if not 0.0 <= ns.m_alpha <= 1.0:
+            p.error('--m_alpha must lie in [0, 1], got %g' % ns.m_alpha)
+        if not ns.m_tau > 0.0:
+            p.error('--m_tau must be > 0 (the softmax temperature), got %g' % ns.m_tau)
+        if not ns.m_clip < 0.0:
+            p.error('--m_clip must be < 0 (the lower clip of tau * log pi), got %g' % ns.m_clip)
     return Config.from_namespace(ns)
 
 

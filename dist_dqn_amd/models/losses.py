@@ -6,7 +6,8 @@ the host at `/root/reference/src/dqn_agent.py:224-253`):
     L  = mean((Q(s, a) - y)^2) + reg_param * sum_w 0.5 ||w||^2
 Extensions: Huber, Double DQN (argmax by the online net), n-step discount
 (gamma_n = gamma ** n), importance weights (PER), the C51 categorical
-projection loss and the QR-DQN quantile regression loss. The L2 term is NOT
+projection loss, the QR-DQN quantile regression loss and the Munchausen-DQN
+soft target (``munchausen_loss``). The L2 term is NOT
 part of these functions: it is applied as ``grad += reg_param * w`` in the
 optimizer (same gradient, no extra pass).
 """
@@ -118,3 +119,36 @@ def qr_loss(theta: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, d
     if weights is not None:
         per = per * weights
     return per.mean(), pr
+
+
+def munchausen_loss(q: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor,
+                    q_next_target: torch.Tensor, q_target: torch.Tensor, gamma, alpha: float = 0.9,
+                    tau: float = 0.03, clip: float = -1.0, kind: str = 'mse', delta: float = 1.0,
+                    weights: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Munchausen-DQN loss (Vieillard, Pietquin, Geist 2020). q: online Q(s, .) [B, A];
+    q_next_target / q_target: the TARGET net on s' and on s. gamma: float or per-row [B] (it
+    carries the n-step power; the bonus is that of the sampled (s, a) only). Returns (loss,
+    |td_error|). With pi = softmax(q_target_net / tau), in max-subtracted form (finite for
+    tau = 0.03 and Q values of a few hundred):
+
+        lp(x, a) = q(x, a) - max_k q(x, k) - tau log sum_k exp((q(x, k) - max_k q(x, k)) / tau)   (= tau log pi, <= 0)
+        soft(x)  = max_k q(x, k) + tau log sum_k exp((q(x, k) - max_k q(x, k)) / tau)
+        y        = r + alpha clip(lp(s, a), l0, 0) + gamma (1 - done) soft(s')
+        td       = y - Q(s, a)
+
+    The per-sample loss, weights and reduction are ``scalar_td_loss``'s; y carries no gradient."""
+    a = actions.long().view(-1, 1)
+    q_sa = q.gather(1, a).squeeze(1)
+    with torch.no_grad():
+        qn, qs = q_next_target.float(), q_target.float()
+        mn, ms = qn.max(dim=1, keepdim=True).values, qs.max(dim=1, keepdim=True).values
+        soft = mn.squeeze(1) + tau * torch.log(torch.exp((qn - mn) / tau).sum(1))
+        lse = tau * torch.log(torch.exp((qs - ms) / tau).sum(1))
+        lp = (qs - ms).gather(1, a).squeeze(1) - lse
+        g = torch.as_tensor(gamma, dtype=torch.float32, device=q.device).reshape(-1)
+        y = rewards.float() + alpha * lp.clamp(clip, 0.0) + g * (1.0 - dones.float()) * soft
+    d = q_sa - y
+    per = elementwise(d, kind, delta)
+    if weights is not None:
+        per = per * weights
+    return per.mean(), d.detach().abs()

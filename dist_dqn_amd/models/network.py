@@ -50,16 +50,20 @@ def make_executor(arch: ArchSpec, layout, config, device: torch.device):
     backend = getattr(config, 'backend', 'auto')
     kw = dict(input_scale=config.input_scale, loss=config.loss, huber_delta=config.huber_delta,
               double_dqn=config.double_dqn)
+    if getattr(config, 'munchausen', False):
+        # Munchausen-DQN: the plain scalar net with another regression target (three hyper-parameters)
+        kw['munchausen'] = (config.m_alpha, config.m_tau, config.m_clip)
     if device.type == 'cuda' and backend in ('auto', 'hip') and not arch.is_conv:
         # MLP nets (the reference SimpleNetwork): one fused fp32 kernel per SGD step
         from ..ops.mlp_executor import HipMlpExecutor, supports_mlp
-        if supports_mlp(arch):
+        if supports_mlp(arch, kw.get('munchausen')):
             return HipMlpExecutor(arch, layout, **kw)
         if backend == 'hip':
-            raise RuntimeError('HIP MLP executor does not support %s' % (arch,))
+            raise RuntimeError('HIP MLP executor does not support %s%s'
+                               % (arch, ' with the Munchausen-DQN target' if 'munchausen' in kw else ''))
     if device.type == 'cuda' and backend in ('auto', 'hip') and arch.is_conv:
         from ..ops.executor import make_hip_executor, supports
-        if supports(arch):
+        if supports(arch, kw.get('munchausen')):
             # --dtype: bf16 / fp16 (16-bit MFMA builds) or fp32 (the reference's precision: the
             # fp32-MFMA build of the same kernels, _C_f32)
             from ..ops.tuning import KernelTuning

@@ -15,7 +15,9 @@ Supported: `nature` convs (84x84x4 uint8 frames), plain or dueling heads,
 scalar (MSE/Huber), C51 distributional (csrc/kernels/rainbow.hip) or QR-DQN
 quantile (csrc/kernels/qr_head.hip; it shares every C51 buffer and launch but the head), noisy
 dense layers (factorised Gaussian: effective weights mixed on the GPU, then
-packed; sigma gradients split from the mu gradients), Double DQN, PER weights.
+packed; sigma gradients split from the mu gradients), Double DQN, PER weights, and the
+Munchausen-DQN target on a scalar net (csrc/kernels/mdqn_head.hip: the rows path of the
+distributional heads with one output per action and a third instance, target(s)).
 The reference `cnn` (SAME convs + max-pools) runs on the per-sample fused
 kernels of csrc/kernels/cnn.hip (`HipCnnExecutor`). `simple` uses torch.
 """
@@ -33,8 +35,11 @@ from . import _ext
 _KIND = dict(C1=1, C2=2, C3=3, DFWD=4, DF32=5, DDGRAD=6, D3=7, D2=8, F1=9, HW=11, DLR=12)
 
 
-def supports(arch) -> bool:
+def supports(arch, munchausen=None) -> bool:
+    """munchausen: the step uses the Munchausen-DQN head (mdqn_head.hip: one wave lane per action)."""
     if arch.network not in ('nature', 'cnn'):
+        return False
+    if munchausen is not None and (arch.distributional or arch.num_actions > 32):
         return False
     if arch.distributional and arch.atoms > 64:     # one wave64 lane per atom (C51) / quantile (QR-DQN)
         return False
@@ -108,8 +113,8 @@ class HipExecutor:
     consumes_slots = True       # conv1 reads the replay frame ring through [B, 4] slot tables
 
     def __init__(self, arch, layout, dtype: str = 'bf16', input_scale: float = 1.0, loss: str = 'mse',
-                 huber_delta: float = 1.0, double_dqn: bool = False, tuning=None):
-        assert supports(arch), 'HIP executor: unsupported architecture'
+                 huber_delta: float = 1.0, double_dqn: bool = False, tuning=None, munchausen=None):
+        assert supports(arch, munchausen), 'HIP executor: unsupported architecture'
         # fp16 (--dtype=fp16) / fp32 (--dtype=fp32, the reference's training precision): the same
         # kernels built with -DDQN_F16 (fp16 MFMA, static loss scale inside the kernels) or
         # -DDQN_F32 (fp32 MFMA); everything else (fp32 master state, layouts) is shared
@@ -132,6 +137,15 @@ class HipExecutor:
         self.dist = arch.distributional
         self.atoms = arch.atoms if self.dist else 1
         self.quantile = arch.quantile     # QR-DQN: atoms = quantiles, no support
+        # Munchausen-DQN (alpha, tau, clip): a scalar net (dist False, atoms 1, the plain parameter
+        # layout) whose step takes the distributional heads' path -- output rows [B][KD] of every
+        # instance from one igemm, the head on those rows, the dH igemm, the grouped output-layer
+        # members -- with the learner instances [online(s), target(s'), target(s)]
+        self.mdqn = None if munchausen is None else tuple(float(v) for v in munchausen)
+        if self.mdqn is not None:
+            from ..models.executor import check_munchausen
+            check_munchausen(arch, double_dqn, *self.mdqn)
+        self.rows = self.dist or self.mdqn is not None      # the head reads precomputed output rows
         self.NO = self.A * self.atoms          # output-layer width (advantage / plain head)
         self.noisy = arch.noisy
         self._eff: Dict[int, torch.Tensor] = {}
@@ -215,7 +229,7 @@ class HipExecutor:
                                       for n, o in fcs])
         hw = 'advantage/output/w' if self.dueling else 'output/w'
         hb = 'advantage/output/b' if self.dueling else 'output/b'
-        if not self.dist:
+        if not self.rows:
             # scalar head: output-layer fragments for the head kernel's MFMA Q tiles
             add('head/w', H, self.NO, [dict(src_off=lay.offsets[hw], K=H, N=self.NO, mode=0)])
             if self.dueling:
@@ -244,7 +258,7 @@ class HipExecutor:
             jobs.append(_Job(src_off=lay.offsets[n + '/b'], K=H, dst_off=off + self.fs * o, mode=3))
         off += self.fs * self.HH
         off = (off + 255) // 256 * 256
-        if self.dist:
+        if self.rows:
             # C51: the combined output layer's bias row (fp32): logits bias | pad | value bias at VO
             self.poff['head/bias'] = off
             jobs.append(_Job(src_off=lay.offsets[hb], K=self.NO, dst_off=off, mode=3))
@@ -892,19 +906,22 @@ class HipExecutor:
         head's dZ rows as act_t: scalar heads dQ [B][64]; C51 dL/dlogits [B][KD] (the dH igemm's
         A operand; its pad columns stay zero from here on)."""
         f32 = dict(dtype=torch.float32, device=dev)
-        width = self.c51_KD if self.dist else 64
+        width = self.c51_KD if self.rows else 64
         return {'loss_parts': torch.zeros(64, **f32), 'dq16': torch.zeros(B * width, dtype=self.act_dtype, device=dev)}
 
     def _loss_parts(self, B):
         """Loss partials the head launch writes: one per 16-sample tile (scalar) or per C51
         learner block (8 samples each, at most 64 blocks)."""
-        return min((B + 7) // 8, 64) if self.dist else (B + 15) // 16
+        return min((B + 7) // 8, 64) if self.rows else (B + 15) // 16
 
     # ------------------------------------------------------------ forward
     @property
     def fused_sampling(self) -> bool:
-        """The fused trunk can draw the uniform minibatch itself (replay.sample_slots(defer))."""
-        return self.fused_trunk
+        """The fused trunk can draw the uniform minibatch itself (replay.sample_slots(defer)). Not for
+        a Munchausen step: the trunk derives next-state slots for every instance after the first,
+        and the third instance there reads the sampled states (the learner then uses a sampler
+        launch, whose two slot tables the three instances read by pointer)."""
+        return self.fused_trunk and self.mdqn is None
 
     def _fwd_trunk(self, xs, packs, flats, ws, B, ninst, frames=None, keep_acts=True, M=(), sample=None, fc=True,
                    fc_zero=None):
@@ -985,7 +1002,7 @@ class HipExecutor:
         """Whether the training step's fc forward and scalar head run as ONE launch
         (csrc/kernels/fc_head.hip): scalar heads with A <= 18, hidden width <= 512, <= 16 fused
         actors, a hidden width % 64 == 0."""
-        return (self.fold_head and not self.dist and self.A <= 18 and self.HID <= 512 and self.HID % 64 == 0
+        return (self.fold_head and not self.rows and self.A <= 18 and self.HID <= 512 and self.HID % 64 == 0
                 and E <= 16 and B <= 1024)
 
     def _fold_ws(self, B, dev) -> dict:
@@ -1072,8 +1089,8 @@ class HipExecutor:
         return ws
 
     def _head(self, ints, hs, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h=0, ws=None):
-        """Output layer + loss (+ backward) launch: scalar head, or the C51 / QR-DQN head."""
-        if self.dist:
+        """Output layer + loss (+ backward) launch: scalar head, or the C51 / QR-DQN / Munchausen head."""
+        if self.rows:
             B, dev = ints[0], ws['dq16'].device
             # (pw, pwv = the combined output layer's fragments and bias rows, see _head_packs)
             if act_h:
@@ -1083,6 +1100,12 @@ class HipExecutor:
             else:
                 lg = self._c51_logits(hs, pw, pwv, B, dev)
             qp = [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()] if not ints[5] else []
+            if self.mdqn is not None:
+                if self.head_prof is not None:
+                    raise RuntimeError('head_prof: the Munchausen head writes no phase stamps (C51 and scalar heads do)')
+                self.ext.qnet_mdqn_head(ints, [1], list(self.mdqn) + [self.delta], hs, w, b, wv, bv, io, [], [],
+                                        zero, actor, actor_f, lg, act_h, qp)
+                return
             if self.quantile:
                 if self.head_prof is not None:
                     raise RuntimeError('head_prof: the QR-DQN head writes no phase stamps (C51 and scalar heads do)')
@@ -1133,7 +1156,7 @@ class HipExecutor:
     def _head_packs(self, packs):
         """Scalar heads: the output layer's fragments (plain / advantage, dueling value); C51: the
         combined output layer's fragments and its fp32 bias row."""
-        if self.dist:
+        if self.rows:
             return ([p.data_ptr() + self.esz * self.poff['head/wc'] for p in packs],
                     [p.data_ptr() + self.esz * self.poff['head/bias'] for p in packs])
         pw = [p.data_ptr() + self.esz * self.poff['head/w'] for p in packs]
@@ -1153,7 +1176,7 @@ class HipExecutor:
         head kernel wrote dH; C51: dH = (dout16 [W | Wv]^T) * (h > 0) is one more igemm launch
         before it, over the head's dL/dlogits rows. draw_noise = (out0, out1, rng): the launch
         also draws the next noisy-net samples (see ``loss_and_grad``)."""
-        if self.dist and not dh_done:
+        if self.rows and not dh_done:
             self._c51_dh(ws, B, po)
         dh, pk, dz3, x3, dims, aux, aux_f = self._fc_dgrad_args(ws, B, po, zero, draw_noise)
         if gather is not None:          # (device XgmiGatherArgs ptr, blocks): the low-rank all-gather duty
@@ -1199,8 +1222,8 @@ class HipExecutor:
         scalar heads dQ (ld 64, value dQ in column 32), C51 dL/dlogits (ld KD, value at VO)."""
         dw, db, dwv, dbv = hgrads
         H, HH = self.HID, self.HH
-        N, NV = (self.NO, self.atoms) if self.dist else (self.A, 1)
-        ld, vo = (self.c51_KD, self.c51_VO) if self.dist else (64, 32)
+        N, NV = (self.NO, self.atoms) if self.rows else (self.A, 1)
+        ld, vo = (self.c51_KD, self.c51_VO) if self.rows else (64, 32)
         dq = ws['dq16'].data_ptr()
         esz = ws['dq16'].element_size()
         adv = [_KIND['HW'], h0 + (esz * H if self.dueling else 0), dq, ld, dw, db, 0, 0, N, N]
@@ -1306,7 +1329,7 @@ class HipExecutor:
         po, pt = self.packed(online), self.packed(target)
         # noisy nets: effective weights under this step's noise (mixed + packed on the GPU)
         eo, et = self.effective(online, noise), self.effective(target, noise_target)
-        ninst = 3 if self.double else 2
+        ninst = 3 if self.double or self.mdqn is not None else 2
         E = 0
         if acting is not None:
             assert frames is not None and self.supports_fused_acting(), 'fused acting needs a slot batch'
@@ -1315,9 +1338,14 @@ class HipExecutor:
         spec = batch.get('sample_spec')
         if spec is not None:
             assert self.fused_trunk and frames is not None, 'deferred sampling needs the fused trunk'
+            # (the trunk derives "next slots" for every instance after the first)
+            assert self.mdqn is None, 'munchausen: the trunk cannot draw the minibatch (fuse_sampling=1)'
+        xs, packs, flats = [s, ns, ns], [po, pt, po], [eo, et, eo]
+        if self.mdqn is not None:          # the third instance: the target net on the sampled states
+            xs, packs, flats = [s, ns, s], [po, pt, pt], [eo, et, et]
         return SimpleNamespace(
             B=B, dev=dev, ws=ws, s=s, frames=frames, po=po, eo=eo, ninst=ninst, acting=acting, E=E, grad=grad_out,
-            xs=[s, ns, ns][:ninst], packs=[po, pt, po][:ninst], flats=[eo, et, eo][:ninst],
+            xs=xs[:ninst], packs=packs[:ninst], flats=flats[:ninst],
             sample=(spec, ninst) if spec is not None else None, fold=self.can_fold_head(B, E),
             g=lambda n: grad_out.data_ptr() + 4 * lay.offsets[n],
             pko=lambda key: po.data_ptr() + self.esz * self.poff[key])
@@ -1370,7 +1398,7 @@ class HipExecutor:
         hints = [B, self.A, self.HID, int(self.dueling), int(self.huber), 0]
         hio = [act.data_ptr(), rew.data_ptr(), done.data_ptr(), gam.data_ptr(),
                wts.data_ptr() if wts is not None else 0, ws['loss'].data_ptr(), ws['prio'].data_ptr(),
-               ws['q'].data_ptr() if not self.dist else 0, *st.hgrads, ws['dh'].data_ptr()]
+               ws['q'].data_ptr() if not self.rows else 0, *st.hgrads, ws['dh'].data_ptr()]
         hactor = [] if acting is None else list(acting['ptrs']) + list(acting['ints'])
         hactor_f = [] if acting is None else list(acting['f'])
         act_h = 0 if acting is None else ws['h'][ninst].data_ptr()
@@ -1498,7 +1526,7 @@ class HipExecutor:
         assert self.lowrank_spec(B, sigma_fused=True) is not None, 'low-rank exchange not available here'
         W, rk = int(lowrank['world']), int(lowrank['rank'])
         lw = self._lowrank_ws(B, W, st.dev)
-        if self.dist:                              # C51: dH = dlogits [W | Wv]^T * (h > 0) first
+        if self.rows:                              # C51: dH = dlogits [W | Wv]^T * (h > 0) first
             self._c51_dh(ws, B, po)
         # in stream order (a graph fork / join costs ~25 us on this ROCm: measured,
         # scripts/probe_graph_concurrency.py), right after the head: x3 and dh are final.
@@ -1530,7 +1558,7 @@ class HipExecutor:
         ext, ws, B = self.ext, st.ws, st.B
         if fl.chain:
             # fc dgrad (+ its side duties) -> conv3 dgrad -> conv2 dgrad: ONE launch
-            if self.dist:                   # C51: dH = dlogits [W | Wv]^T * (h > 0) first
+            if self.rows:                   # C51: dH = dlogits [W | Wv]^T * (h > 0) first
                 self._c51_dh(ws, B, st.po)
             dh, pk, dz3, x3m, dims0, aux0, auxf0 = self._fc_dgrad_args(ws, B, st.po, st.zero, draw_noise)
             three = self.chain_dgrad >= 2       # (2: the conv2 dgrad inside the chain too)

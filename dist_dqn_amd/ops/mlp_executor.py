@@ -18,7 +18,10 @@ _ACT = {None: 0, 'tanh': 1, 'relu': 2}
 MAX_LAYERS, MAX_WIDTH, THREADS = 4, 64, 128
 
 
-def supports_mlp(arch) -> bool:
+def supports_mlp(arch, munchausen=None) -> bool:
+    """munchausen: the Munchausen-DQN target is not in mlp.hip (that step runs on the torch executor)."""
+    if munchausen is not None:
+        return False
     if arch.is_conv or arch.dueling or arch.distributional or arch.noisy:
         return False
     layers = arch.dense_layers()
@@ -34,8 +37,8 @@ class HipMlpExecutor:
     compute_dtype = 'fp32'
 
     def __init__(self, arch, layout, input_scale: float = 1.0, loss: str = 'mse', huber_delta: float = 1.0,
-                 double_dqn: bool = False, **_):
-        assert supports_mlp(arch), 'HIP MLP executor: unsupported architecture'
+                 double_dqn: bool = False, munchausen=None, **_):
+        assert supports_mlp(arch, munchausen), 'HIP MLP executor: unsupported architecture or loss'
         self.ext = _ext.load(required=True)
         self.arch, self.layout = arch, layout
         self.input_scale = float(input_scale)

@@ -43,11 +43,18 @@ class _TDLossHip(torch.autograd.Function):
 def td_loss(out: torch.Tensor, actions, rewards, dones, gammas, next_t, next_o=None,
             weights: Optional[torch.Tensor] = None, kind: str = 'mse', delta: float = 1.0,
             distributional: bool = False, v_min: float = -10.0, v_max: float = 10.0, pure_torch: bool = False,
-            kappa: Optional[float] = None):
+            kappa: Optional[float] = None, munchausen=None, q_target: Optional[torch.Tensor] = None):
     """Returns (mean loss [scalar], per-sample priority [B]). pure_torch: the torch oracle on any
     device (the numerics reference of the HIP kernels). kappa: ``out`` holds QR-DQN quantiles
     [B, A, N]; the quantile loss is the torch function on every device (the HIP training head
-    of the conv executor is csrc/kernels/qr_head.hip)."""
+    of the conv executor is csrc/kernels/qr_head.hip). munchausen = (alpha, tau, clip): the
+    Munchausen-DQN target from ``next_t`` and ``q_target`` (the target net on s' and on s), the
+    torch function on every device too (HIP training head: csrc/kernels/mdqn_head.hip)."""
+    if munchausen is not None:
+        assert q_target is not None and next_o is None and not distributional and kappa is None
+        alpha, tau, clip = munchausen
+        return losses.munchausen_loss(out, actions, rewards, dones, next_t, q_target, gammas, alpha, tau, clip,
+                                      kind, delta, weights)
     if kappa is not None:
         return losses.qr_loss(out, actions, rewards, dones, next_t, next_o, gammas, kappa, weights)
     if out.is_cuda and not pure_torch:
