@@ -134,6 +134,24 @@ void optimizer_step(int64_t op, torch::Tensor w, torch::Tensor grad, torch::Tens
                         (int)target_freq, cur_stream());
 }
 
+// Global-norm clip of the flat gradient in place (grad_clip.hip); stats = [norm, scale] stays on the device.
+void grad_clip(torch::Tensor grad, double max_norm, double grad_scale, torch::Tensor stats, torch::Tensor partials,
+               torch::Tensor counter) {
+  CHECK_T(grad, torch::kFloat32); CHECK_T(stats, torch::kFloat32); CHECK_T(partials, torch::kFloat32);
+  CHECK_T(counter, torch::kInt32);
+  TORCH_CHECK(stats.device() == grad.device() && partials.device() == grad.device() &&
+              counter.device() == grad.device(), "grad_clip: every tensor on the gradient's device");
+  TORCH_CHECK(max_norm > 0.0, "grad_clip: max_norm must be > 0");
+  TORCH_CHECK(grad_scale > 0.0, "grad_clip: grad_scale must be > 0");
+  TORCH_CHECK(grad.numel() >= 1, "grad_clip: empty gradient");
+  TORCH_CHECK(stats.numel() >= 2, "grad_clip: stats holds [norm, scale]");
+  TORCH_CHECK(partials.numel() >= grad_clip_blocks(grad.numel()), "grad_clip: partials shorter than grad_clip_blocks(n)");
+  TORCH_CHECK(counter.numel() >= 1, "grad_clip: counter is one int32");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(grad.device());
+  launch_grad_clip(ptr<float>(grad), grad.numel(), (float)max_norm, (float)grad_scale, ptr<float>(stats),
+                   ptr<float>(partials), ptr<int32_t>(counter), cur_stream());
+}
+
 // ---- optim_pack: the optimizer step fused with the executor's weight packing (optim.hip
 // optim_pack_kernel). OptimPackArgs (dqn_kernels.h) documents the arguments; each helper below
 // checks one group of them and fills its fields.
@@ -799,6 +817,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("has_step"), pybind11::arg("hp"), pybind11::arg("target") = pybind11::none(),
         pybind11::arg("target_freq") = 1);
   m.def("target_update", &target_update);
+  m.def("grad_clip", &grad_clip, pybind11::arg("grad"), pybind11::arg("max_norm"), pybind11::arg("grad_scale"),
+        pybind11::arg("stats"), pybind11::arg("partials"), pybind11::arg("counter"));
+  m.def("grad_clip_blocks", [](int64_t n) { return (int64_t)grad_clip_blocks(n); });
   m.def("optim_pack", &optim_pack, pybind11::arg("op"), pybind11::arg("w"), pybind11::arg("grad"),
         pybind11::arg("s0"), pybind11::arg("s1"), pybind11::arg("beta_pow"), pybind11::arg("ticket"),
         pybind11::arg("lr"), pybind11::arg("reg"), pybind11::arg("reg_end"), pybind11::arg("grad_scale"),

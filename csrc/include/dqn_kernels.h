@@ -43,6 +43,12 @@ void launch_sumtree_sample(const float* sum, const float* mn, int64_t* rng, cons
 void launch_optimizer_step(int op, float* w, const float* g, float* s0, float* s1, float* beta_pow,
                            int64_t* step, int32_t* ticket, const float* hp9, float lr, float reg, int reg_end,
                            float grad_scale, int n, float* tgt, int tfreq, hipStream_t st);
+// Global gradient-norm clipping of n fp32 values (grad_clip.hip): stats[0] = grad_scale * ||grad||_2,
+// stats[1] = max_norm / max(stats[0], max_norm) (0 when the norm is not finite), grad *= stats[1].
+// partials: grad_clip_blocks(n) floats; counter: one zeroed int32 (the kernel leaves it zero).
+int grad_clip_blocks(int64_t n);
+void launch_grad_clip(float* grad, int64_t n, float max_norm, float grad_scale, float* stats, float* partials,
+                      int32_t* counter, hipStream_t st);
 // The fc (hidden dense) layer's weight gradient formed inside the optimizer launch (optim.hip):
 // dW[k][n] = sum_{m < M} x[m][k] dh[m][col + n] for the update jobs that carry a dH column
 // (UpdJob.fc_col >= 0), and the fc bias gradient sum_m dh[m][col + n] -- never written to the

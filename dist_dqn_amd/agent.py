@@ -205,6 +205,9 @@ class DQNAgent:
             # reference summary `loss` = TD loss + reg_param * L2 (network.py:149-155)
             self.network.last_loss = loss
             self.summary_writer.add_scalar('loss', self.network.total_loss(), self.training_steps)
+            if getattr(self.config, 'max_grad_norm', 0.0) > 0.0 and self.network.grad_norm is not None:
+                # the pre-clip global norm of this step's gradient (read where the loss is read)
+                self.summary_writer.add_scalar('grad_norm', float(self.network.grad_norm), self.training_steps)
         self.training_steps += 1
         if not self._device_replay:
             if self.config.target_update_tau < 1.0:

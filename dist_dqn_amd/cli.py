@@ -291,6 +291,8 @@ def _run_device_envs(config: Config, ctx, env, network, sv, seed: int):
                               replay_size=replay.size())
                 if writer is not None:
                     writer.add_scalar('loss', loss, learner.train_steps)
+                    if learner.grad_norm is not None:      # --max_grad_norm: the pre-clip norm
+                        writer.add_scalar('grad_norm', float(learner.grad_norm), learner.train_steps)
                 log.info('training steps = %d, %.0f SGD steps/s, %.0f env frames/s, epsilon = %.3f, loss = %.4f',
                          learner.train_steps, rate, fps, actor.epsilon, loss)
                 t_log, f_log, s_log = now, fr, learner.train_steps

@@ -129,6 +129,11 @@ def build_parser() -> argparse.ArgumentParser:
     a('--m_alpha', default=0.9, type=float, help='Munchausen bonus weight alpha (0 <= alpha <= 1)')
     a('--m_tau', default=0.03, type=float, help='Munchausen softmax temperature tau (> 0)')
     a('--m_clip', default=-1.0, type=float, help='Munchausen lower clip l0 of tau * log pi (< 0)')
+    a('--max_grad_norm', default=0.0, type=float,
+      help='Clip the loss gradient of all trainable parameters by its global L2 norm (TensorFlow '
+           'clip_by_global_norm: g *= C / max(||g||, C), after the data-parallel average; the decoupled L2 '
+           'term stays unclipped; a non-finite norm applies no gradient). 0 = off. A clipped run gives up '
+           'the fused weight-gradient / update launches (--fuse_fc_wgrad, --fuse_wgrad_update, --det_wgrad)')
     a('--noisy', action='store_true', help='Factorised-Gaussian noisy FC layers')
     a('--noisy_sigma0', default=0.5, type=float)
     a('--target_update_tau', default=1.0, type=float,
@@ -215,7 +220,7 @@ def build_parser() -> argparse.ArgumentParser:
            'atomics: bit-reproducible steps; measured 79.6 vs 71.4 us per flagship step, so opt-in)')
     a('--kernel_tuning', default='',
       help='HIP executor tuning constants, "key=value,..." (ops/tuning.py KernelTuning: wg_conv_chunks, '
-           'dep_at, fold_two_per_cu, tfact); empty = the measured defaults')
+           'dep_at, fold_two_per_cu, tfact, cnn_bwd_parts); empty = the measured defaults')
     a('--checkpoint_secs', default=600, type=float,
       help='chief: seconds between periodic checkpoints (reference Supervisor: 600; <= 0 disables)')
     a('--max_to_keep', default=5, type=int)
@@ -299,6 +304,7 @@ class Config:
     m_alpha: float = 0.9
     m_tau: float = 0.03
     m_clip: float = -1.0
+    max_grad_norm: float = 0.0
     noisy: bool = False
     noisy_sigma0: float = 0.5
     target_update_tau: float = 1.0
@@ -384,6 +390,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> Config:
             p.error('--m_tau must be > 0 (the softmax temperature), got %g' % ns.m_tau)
         if not ns.m_clip < 0.0:
             p.error('--m_clip must be < 0 (the lower clip of tau * log pi), got %g' % ns.m_clip)
+    if ns.max_grad_norm < 0.0 or ns.max_grad_norm != ns.max_grad_norm:
+        p.error('--max_grad_norm must be >= 0 (0 = no clipping), got %g' % ns.max_grad_norm)
+    if ns.max_grad_norm > 0.0 and ns.async_ps:
+        p.error('--max_grad_norm and --async_ps cannot be combined: the parameter server applies the workers\' '
+                'pushes in arrival order, so the clip belongs on the server, which does not clip')
     return Config.from_namespace(ns)
 
 

@@ -105,15 +105,23 @@ class Learner:
         # the fc weight / bias gradient formed inside the fused optimizer launch from the fc input
         # rows and dH rows (executor.can_defer_fc): no fp32 fc gradient round trip through HBM.
         # Under DP only with the low-rank exchange (the rows are then every rank's)
-        sg = not (ps_client is None and network.fuses_sigma_grads(tfreq))
-        self._defer_fc = bool(ps_client is None and int(getattr(config, 'fuse_fc_wgrad', 1))
+        # --max_grad_norm: the clip (Network.clip_grads, between the all-reduce and the optimizer) needs
+        # the complete loss gradient in the flat buffer: explicit sigma gradients, and none of the paths
+        # that leave a weight gradient to the optimizer launch (defer_fc / defer_wgrad / det_wgrad / the
+        # fused DP exchange). The low-rank fc exchange stays: its summed fc gradient lands in the flat buffer
+        self._clip = float(getattr(config, 'max_grad_norm', 0.0) or 0.0)
+        assert self._clip == 0.0 or ps_client is None, '--max_grad_norm: the async parameter server does not clip'
+        clip = self._clip > 0.0
+        sigma_fused = network.fuses_sigma_grads(tfreq) and not clip
+        sg = not (ps_client is None and sigma_fused)
+        self._defer_fc = bool(ps_client is None and not clip and int(getattr(config, 'fuse_fc_wgrad', 1))
                               and network.fuses_update(tfreq) and hasattr(ex, 'can_defer_fc')
                               and ex.can_defer_fc(B, sg))
         lr = None
         if (self.ctx.enabled and ps_client is None and int(getattr(config, 'lowrank_dense', 1))
                 and getattr(config, 'overlap_allreduce', True) and hasattr(ex, 'lowrank_spec')
                 and getattr(config, 'allreduce_dtype', 'fp32') == 'fp32'):
-            lr = ex.lowrank_spec(B, sigma_fused=network.fuses_sigma_grads(tfreq), fused_fc=self._defer_fc)
+            lr = ex.lowrank_spec(B, sigma_fused=sigma_fused, fused_fc=self._defer_fc)
         # data parallelism, fused step: the conv / output-layer weight gradients run inside the update
         # launch as in one process, and its dependent update jobs sum them over the ranks in-launch (the
         # xgmi transport's exchange channel, optim_pack.h kModeDp): no all-reduce launch, no separate
@@ -151,7 +159,8 @@ class Learner:
         # conv weight gradients as deterministic chunk-group partials summed inside the fused
         # optimizer launch (executor.can_det_wgrad): one process only (DP all-reduces the flat
         # gradient, whose conv range then must hold the sums)
-        self._det_wgrad = bool(not self.ctx.enabled and ps_client is None and int(getattr(config, 'det_wgrad', 0))
+        self._det_wgrad = bool(not self.ctx.enabled and ps_client is None and not clip
+                               and int(getattr(config, 'det_wgrad', 0))
                                and network.fuses_update(tfreq) and hasattr(ex, 'can_det_wgrad')
                                and ex.can_det_wgrad(B))
         # the grouped conv / output-layer weight gradients run in the leading blocks of the fused
@@ -230,7 +239,8 @@ class Learner:
             assert 'frames' in batch, 'fused acting needs the slot-batch sampler'
             acting = self.actor.fused_args(defer_per=self._defer_per_insert())
         # noisy nets: the fused optimizer derives dL/dsigma itself (not for async-PS pushes)
-        sg = not (self.ps is None and self.net.fuses_sigma_grads(self._target_freq()))
+        # (a clipped step too: the norm covers the explicit sigma gradients)
+        sg = not (self.ps is None and self._clip == 0.0 and self.net.fuses_sigma_grads(self._target_freq()))
         if self._split:
             loss, prio, self._tail = self.net.compute_grads(batch, acting=acting, split=True, sigma_grads=sg,
                                                             lowrank=self._lowrank, defer_fc=self._defer_fc,
@@ -281,7 +291,13 @@ class Learner:
                 self.B, per=(self.idx, self.prio, self.net.global_step, cfg.per_eps, cfg.per_beta0,
                              cfg.per_beta_steps) if per else None,
                 insert=self.actor.per_insert_spec() if per and self._defer_per_insert() else None)
-        fused = self.net.apply_grads(self.reducer.scale, target_freq=self._target_freq(), next_sample=nxt)
+        if self._clip > 0.0:
+            # g *= C / max(||g * grad_scale||, C): two launches, the scale stays on the device
+            self.net.clip_grads(self._clip, self.reducer.scale)
+            fused = self.net.apply_grads(self.reducer.scale, target_freq=self._target_freq(), next_sample=nxt,
+                                         sigma_from_grad=True)
+        else:
+            fused = self.net.apply_grads(self.reducer.scale, target_freq=self._target_freq(), next_sample=nxt)
         self._presampled = nxt is not None and fused
         if per and not self._presampled:
             self.replay.update_priorities(self.idx, self.prio, cfg.per_eps)
@@ -349,6 +365,12 @@ class Learner:
         else:
             self.reducer.allreduce()
         self._apply()
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """--max_grad_norm: the last step's pre-clip global gradient norm (device tensor, no host
+        sync); None when the run does not clip."""
+        return self.net.grad_norm if self._clip > 0.0 else None
 
     @property
     def stop_requested(self) -> bool:

@@ -224,14 +224,46 @@ class Network:
                 break
         return 0, end
 
+    def clip_grads(self, max_norm: float, grad_scale: float = 1.0, grad: Optional[torch.Tensor] = None):
+        """Global-norm clip of the flat gradient in place (``--max_grad_norm``; ``ops.kernels.grad_clip``):
+        g *= max_norm / max(||g * grad_scale||_2, max_norm), between ``compute_grads(sigma_grads=True)``
+        (and the all-reduce) and ``apply_grads(grad_scale, sigma_from_grad=True)``. Every executor's
+        step goes through here: HIP flat gradients through the clip kernels, CPU tensors and
+        ``--backend=torch`` through the same formula in torch ops. Returns the device ``[norm, scale]``
+        pair (``grad_norm`` is its first element); no host sync."""
+        g = self.grad if grad is None else grad
+        st = getattr(self, '_clip_stats', None)
+        if st is None:
+            # persistent (static under graph capture): [norm, scale], one fp32 partial per block, the
+            # arrival counter (zero between launches)
+            st = self._clip_stats = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self._clip_hip = g.is_cuda and getattr(self.config, 'backend', 'auto') != 'torch'
+            self._clip_partials = self._clip_counter = None
+            if self._clip_hip:
+                ext = getattr(self.executor, 'ext', None)
+                self._clip_partials = torch.zeros(kernels.grad_clip_blocks(g.numel(), ext), dtype=torch.float32,
+                                                  device=self.device)
+                self._clip_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        kernels.grad_clip(g, float(max_norm), float(grad_scale), st, self._clip_partials, self._clip_counter,
+                          ext=getattr(self.executor, 'ext', None), backend='auto' if self._clip_hip else 'torch')
+        return st
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """The pre-clip global norm of the last ``clip_grads`` (device tensor); None before the first."""
+        st = getattr(self, '_clip_stats', None)
+        return st[0] if st is not None else None
+
     def apply_grads(self, grad_scale: float = 1.0, target_freq: Optional[int] = None, next_sample=None,
-                    grad: Optional[torch.Tensor] = None, repack: bool = True) -> bool:
+                    grad: Optional[torch.Tensor] = None, repack: bool = True, sigma_from_grad: bool = False) -> bool:
         """Optimizer step (global_step += 1 inside it) + executor repack.
 
         target_freq: also do the hard target sync (target <- online when the new
         global_step % target_freq == 0, device predicate) inside those same two
         launches. Returns True when it was fused that way; otherwise the caller
-        still owes the target update (``hard_target_update``). next_sample: ``(spec, B)`` — the
+        still owes the target update (``hard_target_update``). sigma_from_grad (noisy nets, after
+        ``compute_grads(sigma_grads=True)``; a clipped step): the fused optimizer reads the sigma
+        gradients from the buffer instead of deriving them from the mu gradients. next_sample: ``(spec, B)`` — the
         fused launch also draws the next uniform minibatch (only honoured when it returns True).
         grad: the gradient buffer to apply (default ``self.grad``; the xgmi parameter server passes
         a worker's peer-written slot). repack=False (the parameter server, which never runs the
@@ -255,8 +287,8 @@ class Network:
                     self._noise_drawn = False
                 else:
                     self.executor.draw_noise(self.noise_next, self.noise_target, self.noise_rng)
-                kw.update(noise=self.noise_next, grad_noise=self.noise, noise_dst=self.noise,
-                          target_noise=self.noise_target)
+                kw.update(noise=self.noise_next, grad_noise=None if sigma_from_grad else self.noise,
+                          noise_dst=self.noise, target_noise=self.noise_target)
             ex.update_and_pack(self.optimizer, self.online.flat, g, grad_scale, self.global_step,
                                target=self.target.flat, target_freq=int(target_freq), next_sample=next_sample, **kw)
             return True
@@ -307,6 +339,9 @@ class Network:
 
     def train_step(self, batch: Dict[str, torch.Tensor], grad_scale: float = 1.0):
         loss, prio = self.compute_grads(batch)
+        c = float(getattr(self.config, 'max_grad_norm', 0.0) or 0.0)
+        if c > 0.0:
+            self.clip_grads(c, grad_scale)
         self.apply_grads(grad_scale)
         return loss, prio
 

@@ -164,6 +164,39 @@ def optimizer_step(opt, param: torch.Tensor, grad: torch.Tensor, grad_scale: flo
                        target, int(target_freq))
 
 
+# ------------------------------------------------------- gradient clipping
+def grad_clip_blocks(n: int, ext=None) -> int:
+    """Blocks (= fp32 partial slots) the clip kernels launch for ``n`` values."""
+    ext = ext if ext is not None else _ext.load(required=True)
+    return int(ext.grad_clip_blocks(int(n)))
+
+
+def grad_clip(grad: torch.Tensor, max_norm: float, grad_scale: float, stats: torch.Tensor,
+              partials: Optional[torch.Tensor] = None, counter: Optional[torch.Tensor] = None,
+              ext=None, backend: str = 'auto'):
+    """TensorFlow's clip_by_global_norm on the flat gradient, in place, with no host sync:
+    ``stats[0] = norm = grad_scale * ||grad||_2`` (the gradient as the optimizer consumes it),
+    ``stats[1] = scale = max_norm / max(norm, max_norm)`` (exactly 1 when norm <= max_norm; 0 when
+    the norm is not finite: the step then applies no loss gradient), ``grad *= scale``.
+    GPU: two HIP launches (csrc/kernels/grad_clip.hip; ``partials`` >= ``grad_clip_blocks(n)``
+    floats, ``counter`` one zeroed int32 the kernel leaves zero; ``ext``: the executor's build).
+    CPU tensors, or ``backend='torch'``: the same formula in torch ops (float64 accumulation)."""
+    if not max_norm > 0.0:
+        raise ValueError('grad_clip: max_norm must be > 0, got %r' % (max_norm,))
+    if grad.is_cuda and backend != 'torch':
+        ext = ext if ext is not None else _ext.load(required=True)
+        ext.grad_clip(grad, float(max_norm), float(grad_scale), stats, partials, counter)
+        return stats
+    norm = (torch.linalg.vector_norm(grad, dtype=torch.float64).to(torch.float32) * float(grad_scale)).view(())
+    c = torch.full_like(norm, float(max_norm))
+    scale = torch.where(torch.isfinite(norm), c / torch.maximum(norm, c), torch.zeros_like(norm))
+    stats[0] = norm
+    stats[1] = scale
+    # (scale 0: zeros, not NaN * 0; scale 1: the same bits)
+    grad.copy_(torch.where(scale == 0.0, torch.zeros_like(grad), grad * scale))
+    return stats
+
+
 # ---------------------------------------------------------- target network
 def target_update(dst: torch.Tensor, src: torch.Tensor, tau: float,
                   step: Optional[torch.Tensor] = None, freq: int = 1, extra: Optional[tuple] = None):
