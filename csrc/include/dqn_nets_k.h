@@ -120,7 +120,7 @@ struct HeadArgs {
   const void* act_h;             // training mode + fused acting: the actors' hidden layer [E][HH]
   int act_E;                     //   (an extra workgroup runs the acting step), 0 = off
   int atoms;                     // C51 head (rainbow.hip): atoms per action, support [vmin, vmax];
-                                 // QR-DQN head (qr_head.hip): quantiles per action, kappa in delta
+                                 // QR-DQN heads (qr_head.hip, qr_wide_head.hip): quantiles per action, kappa in delta
   float vmin, vmax;
   int64_t* prof;                 // optional s_memtime phase stamps of block 0 (profiling)
   const float* lgi[3];           // C51: precomputed logits rows [B][KD] per instance (one igemm over the
@@ -294,6 +294,10 @@ int c51_train_blocks(const dqn::HeadArgs& a);     // learner blocks = loss parti
 void launch_qr_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t qr_head_lds_bytes(const dqn::HeadArgs& a);
 int qr_train_blocks(const dqn::HeadArgs& a);
+// Wide QR-DQN head (qr_wide_head.hip): 64 < quantiles <= 256, % 4 == 0; same arguments and outputs
+void launch_qr_wide_head(const dqn::HeadArgs& a, hipStream_t st);
+size_t qr_wide_head_lds_bytes(const dqn::HeadArgs& a);
+int qr_wide_train_blocks(const dqn::HeadArgs& a);  // learner blocks = loss partials: min(B, 64)
 // Munchausen-DQN head (mdqn_head.hip): HeadArgs::m_alpha / m_tau / m_clip, Huber threshold in delta
 void launch_mdqn_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t mdqn_head_lds_bytes(const dqn::HeadArgs& a);

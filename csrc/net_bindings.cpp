@@ -436,6 +436,40 @@ void qr_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<d
   launch_qr_head(a, cur_stream());
 }
 
+// Wide QR-DQN head (qr_wide_head.hip): the arguments of qr_head, for 64 < quantiles <= 256 with
+// quantiles % 4 == 0 (a lane reads four consecutive quantiles of a row as one 16-byte load)
+void qr_wide_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<double> flts, std::vector<int64_t> h,
+                  std::vector<int64_t> w, std::vector<int64_t> b, std::vector<int64_t> wv, std::vector<int64_t> bv,
+                  std::vector<int64_t> io, std::vector<int64_t> pw, std::vector<int64_t> pwv, std::vector<int64_t> zero,
+                  std::vector<int64_t> actor, std::vector<double> actor_f, std::vector<int64_t> lg, int64_t act_h,
+                  std::vector<int64_t> qp) {
+  TORCH_CHECK(dist.size() == 1 && flts.size() == 1, "qr args");
+  dqn::HeadArgs a = head_args(ints, h, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h);
+  a.atoms = (int)dist[0]; a.delta = (float)flts[0];
+  TORCH_CHECK(a.atoms >= 68 && a.atoms <= 256 && a.atoms % 4 == 0,
+              "wide QR-DQN: 68..256 quantiles, a multiple of 4 (four quantiles per 16-byte load), got ", a.atoms);
+  TORCH_CHECK(a.delta > 0.f, "wide QR-DQN: kappa > 0");
+  TORCH_CHECK(qr_wide_head_lds_bytes(a) <= 160 * 1024, "wide QR head: batch too large for one workgroup's LDS");
+  if (!a.infer) {
+    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, "wide QR training: loss partials, dout16, prio");
+    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0, "wide QR training: actions, rewards, dones, gammas");
+    a.loss_parts = P<float*>(qp[0]);
+    a.dq16 = P<void*>(qp[1]);
+  }
+  if (a.act_E > 0) {
+    TORCH_CHECK(!lg.empty(), "wide qr fused acting: the actors' quantile rows");
+    TORCH_CHECK(lg.back() != 0 && lg.back() % 16 == 0, "wide qr fused acting: quantile rows 16-byte aligned");
+    a.act_lgi = P<const float*>(lg.back());
+    lg.pop_back();
+  }
+  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 2 || lg.size() == 3), "wide qr: quantile rows of every instance");
+  for (size_t i = 0; i < lg.size(); ++i) {
+    TORCH_CHECK(lg[i] != 0 && lg[i] % 16 == 0, "wide qr: quantile rows non-null, 16-byte aligned");
+    a.lgi[i] = P<const float*>(lg[i]);
+  }
+  launch_qr_wide_head(a, cur_stream());
+}
+
 // Munchausen-DQN head (mdqn_head.hip): the arguments of qr_head with dist = [1] (one output per
 // action), flts = [alpha, tau, clip, huber_delta]; lg = the scalar output rows of online(s),
 // target(s'), target(s) (training) or of the one acting / q_values instance
@@ -567,6 +601,11 @@ void register_net_ops(pybind11::module_& m) {
         pybind11::arg("actor_f"), pybind11::arg("prof") = 0, pybind11::arg("lg") = std::vector<int64_t>{},
         pybind11::arg("act_h") = 0, pybind11::arg("qp") = std::vector<int64_t>{});
   m.def("qnet_qr_head", &qr_head, pybind11::arg("ints"), pybind11::arg("dist"), pybind11::arg("flts"),
+        pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("b"), pybind11::arg("wv"), pybind11::arg("bv"),
+        pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
+        pybind11::arg("actor_f"), pybind11::arg("lg") = std::vector<int64_t>{}, pybind11::arg("act_h") = 0,
+        pybind11::arg("qp") = std::vector<int64_t>{});
+  m.def("qnet_qr_wide_head", &qr_wide_head, pybind11::arg("ints"), pybind11::arg("dist"), pybind11::arg("flts"),
         pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("b"), pybind11::arg("wv"), pybind11::arg("bv"),
         pybind11::arg("io"), pybind11::arg("pw"), pybind11::arg("pwv"), pybind11::arg("zero"), pybind11::arg("actor"),
         pybind11::arg("actor_f"), pybind11::arg("lg") = std::vector<int64_t>{}, pybind11::arg("act_h") = 0,

@@ -121,7 +121,8 @@ def build_parser() -> argparse.ArgumentParser:
     a('--v_min', default=-10.0, type=float)
     a('--v_max', default=10.0, type=float)
     a('--quantile', action='store_true', help='QR-DQN head (quantile regression; no --v_min/--v_max support)')
-    a('--num_quantiles', default=32, type=int, help='QR-DQN quantiles per action (HIP executor: 2..64)')
+    a('--num_quantiles', default=32, type=int, help='QR-DQN quantiles per action (HIP executor: 2..64, or 68..256 in multiples of 4, e.g. the '
+                                                         'paper\'s 200; other counts run on the torch executor)')
     a('--qr_kappa', default=1.0, type=float, help='QR-DQN Huber threshold kappa (> 0)')
     a('--munchausen', action='store_true',
       help='Munchausen-DQN target (Vieillard et al. 2020): soft next-state value + alpha * clipped tau * log pi(a|s) '
@@ -372,7 +373,7 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> Config:
         if ns.distributional:
             p.error('--quantile and --distributional select different distributional heads: give one')
         if ns.num_quantiles < 2:
-            p.error('--num_quantiles must be at least 2 (the HIP executor takes 2..64), got %d' % ns.num_quantiles)
+            p.error('--num_quantiles must be at least 2 (the HIP executor takes 2..64, and 68..256 in multiples of 4), got %d' % ns.num_quantiles)
         if not ns.qr_kappa > 0.0:
             p.error('--qr_kappa must be > 0 (the Huber threshold of the quantile loss), got %g' % ns.qr_kappa)
     if ns.munchausen:

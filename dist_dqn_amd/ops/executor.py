@@ -13,7 +13,8 @@ target's packed copy is refreshed by a predicated copy when the target syncs.
 
 Supported: `nature` convs (84x84x4 uint8 frames), plain or dueling heads,
 scalar (MSE/Huber), C51 distributional (csrc/kernels/rainbow.hip) or QR-DQN
-quantile (csrc/kernels/qr_head.hip; it shares every C51 buffer and launch but the head), noisy
+quantile (csrc/kernels/qr_head.hip, and qr_wide_head.hip for 68..256 quantiles in multiples of 4;
+it shares every C51 buffer and launch but the head), noisy
 dense layers (factorised Gaussian: effective weights mixed on the GPU, then
 packed; sigma gradients split from the mu gradients), Double DQN, PER weights, and the
 Munchausen-DQN target on a scalar net (csrc/kernels/mdqn_head.hip: the rows path of the
@@ -42,7 +43,9 @@ def supports(arch, munchausen=None) -> bool:
     if munchausen is not None and (arch.distributional or arch.num_actions > 32):
         return False
     if arch.distributional and arch.atoms > 64:     # one wave64 lane per atom (C51) / quantile (QR-DQN)
-        return False
+        # the wide QR-DQN head (qr_wide_head.hip): four quantiles per 16-byte load, up to 256
+        if not (arch.quantile and arch.atoms <= 256 and arch.atoms % 4 == 0):
+            return False
     if tuple(arch.input_shape) != (84, 84, 4):
         return False
     return True
@@ -911,7 +914,10 @@ class HipExecutor:
 
     def _loss_parts(self, B):
         """Loss partials the head launch writes: one per 16-sample tile (scalar) or per C51
-        learner block (8 samples each, at most 64 blocks)."""
+        learner block (8 samples each, at most 64 blocks; the wide QR-DQN head: one sample per
+        block at a time, at most 64 blocks)."""
+        if self.quantile and self.atoms > 64:
+            return min(B, 64)
         return min((B + 7) // 8, 64) if self.rows else (B + 15) // 16
 
     # ------------------------------------------------------------ forward
@@ -1109,8 +1115,9 @@ class HipExecutor:
             if self.quantile:
                 if self.head_prof is not None:
                     raise RuntimeError('head_prof: the QR-DQN head writes no phase stamps (C51 and scalar heads do)')
-                self.ext.qnet_qr_head(ints, [self.atoms], [float(self.arch.kappa)], hs, w, b, wv, bv, io, [], [],
-                                      zero, actor, actor_f, lg, act_h, qp)
+                head = self.ext.qnet_qr_wide_head if self.atoms > 64 else self.ext.qnet_qr_head
+                head(ints, [self.atoms], [float(self.arch.kappa)], hs, w, b, wv, bv, io, [], [],
+                     zero, actor, actor_f, lg, act_h, qp)
                 return
             prof = self.head_prof.data_ptr() if self.head_prof is not None and not ints[5] else 0
             self.ext.qnet_c51_head(ints, [self.atoms], [float(self.arch.v_min), float(self.arch.v_max)], hs, w, b,
