@@ -75,6 +75,33 @@ void replay_gather_frames(torch::Tensor frames, torch::Tensor state_idx, torch::
                               ptr<int32_t>(idx), ptr<uint8_t>(s), ptr<uint8_t>(ns), B, HW, K, sc, cur_stream());
 }
 
+// Randomly shifted frame stacks of a sampled minibatch (augment.hip): frames [F, H, W] u8, slot tables
+// [B, 4] i32, ctr int64 [>= 1] (element 0 is read on the device), out_s / out_ns [B, H, W, 4] u8,
+// shifts [B, 2, 2] i32.
+void replay_gather_shift(torch::Tensor frames, torch::Tensor st_slots, torch::Tensor nx_slots, int64_t seed,
+                         torch::Tensor ctr, int64_t pad, torch::Tensor s, torch::Tensor ns, torch::Tensor shifts) {
+  CHECK_T(frames, torch::kUInt8); CHECK_T(st_slots, torch::kInt32); CHECK_T(nx_slots, torch::kInt32);
+  CHECK_T(ctr, torch::kInt64); CHECK_T(s, torch::kUInt8); CHECK_T(ns, torch::kUInt8); CHECK_T(shifts, torch::kInt32);
+  TORCH_CHECK(frames.dim() == 3 && frames.size(0) >= 1, "frames [F,H,W]");
+  TORCH_CHECK(st_slots.dim() == 2 && st_slots.size(1) == 4, "slot tables must be [B, 4] (frames_per_state = 4)");
+  const int64_t B = st_slots.size(0), F = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(B >= 1 && B <= 1024, "gather_shift batch must be in [1, 1024]");
+  TORCH_CHECK(nx_slots.numel() == B * 4, "next slot table must be [B, 4]");
+  TORCH_CHECK(H >= 1 && W >= 4 && W % 4 == 0, "frame width must be a multiple of 4");
+  TORCH_CHECK(F * H * W < (int64_t(1) << 40) && H * W < (int64_t(1) << 28), "frame ring too large");
+  TORCH_CHECK(pad >= 0 && pad <= 16, "pad must be in [0, 16]");
+  TORCH_CHECK(ctr.numel() >= 1, "ctr: a device int64");
+  TORCH_CHECK(s.numel() == B * H * W * 4 && ns.numel() == s.numel(), "output stacks must be [B, H, W, 4]");
+  TORCH_CHECK(shifts.numel() == B * 4, "shifts must be [B, 2, 2]");
+  TORCH_CHECK(s.device() == frames.device() && ns.device() == frames.device() && ctr.device() == frames.device() &&
+              st_slots.device() == frames.device() && nx_slots.device() == frames.device() &&
+              shifts.device() == frames.device(), "gather_shift: one device");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(frames.device());
+  launch_replay_gather_shift(ptr<uint8_t>(frames), ptr<int32_t>(st_slots), ptr<int32_t>(nx_slots), (uint64_t)seed,
+                             ptr<int64_t>(ctr), (int)pad, ptr<uint8_t>(s), ptr<uint8_t>(ns), ptr<int32_t>(shifts),
+                             (int)B, (int)H, (int)W, (int)F, cur_stream());
+}
+
 void sumtree_set(torch::Tensor sum, torch::Tensor mn, torch::Tensor maxp, torch::Tensor idx, torch::Tensor td,
                  double alpha, double eps, bool use_max, int64_t P) {
   CHECK_T(sum, torch::kFloat32); CHECK_T(mn, torch::kFloat32); CHECK_T(maxp, torch::kFloat32);
@@ -809,6 +836,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("XGMI_MAX_BLOCKS") = dqn::kXgmiMaxBlocks;
   m.attr("XGMI_SIG_WORDS") = dqn::kXgmiMaxRanks * dqn::kXgmiMaxBlocks;
   m.def("replay_gather_frames", &replay_gather_frames);
+  m.def("replay_gather_shift", &replay_gather_shift);
   m.def("sumtree_set", &sumtree_set);
   m.def("sumtree_sample", &sumtree_sample);
   m.def("optimizer_step", &optimizer_step, pybind11::arg("op"), pybind11::arg("w"), pybind11::arg("grad"),

@@ -35,6 +35,13 @@ struct GatherScalars {   // optional per-sample scalar gather (a_out == nullptr:
 void launch_replay_gather_frames(const uint8_t* frames, const int32_t* state_idx, const int32_t* next_idx,
                                  const int32_t* idx, uint8_t* s, uint8_t* ns, int B, int HW, int K,
                                  const GatherScalars& sc, hipStream_t st);
+// DrQ random-shift augmentation fused into the stack gather (augment.hip): both NHWC uint8 stacks
+// [B][H][W][4] of the minibatch whose [B][4] slot tables a sampler wrote, each stack shifted by the
+// (dy, dx) in [-pad, pad] that philox(seed ^ "augm", ctr[0], b, which) draws (edge replication);
+// shifts [B][2][2] receives the pairs. frames [F][H][W], W % 4 == 0; pad = 0: the plain gather.
+void launch_replay_gather_shift(const uint8_t* frames, const int32_t* st_slots, const int32_t* nx_slots,
+                                uint64_t seed, const int64_t* ctr, int pad, uint8_t* out_s, uint8_t* out_ns,
+                                int32_t* shifts, int B, int H, int W, int F, hipStream_t st);
 void launch_sumtree_set(float* sum, float* mn, float* maxp, const int32_t* idx, const float* td, float alpha,
                         float eps, int use_max, int n, int P, hipStream_t st);
 void launch_sumtree_sample(const float* sum, const float* mn, int64_t* rng, const int32_t* size,

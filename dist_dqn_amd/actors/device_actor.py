@@ -68,6 +68,9 @@ class DeviceActor:
     def can_fuse(self, batch_size: int) -> bool:
         """One acting step per learner step that the learner's launches can carry."""
         ex = self.net.executor
+        if getattr(self.cfg, 'augment', 'none') == 'shift' and not getattr(ex, 'supports_mixed_inputs', lambda: False)():
+            # the learner instances read shifted stacks, the actors the ring: needs per-instance loaders
+            return False
         return (self.steps == 1 and self.E <= min(64, batch_size) and getattr(ex, 'consumes_slots', False)
                 and hasattr(ex, 'supports_fused_acting') and ex.supports_fused_acting())
 

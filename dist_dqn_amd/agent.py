@@ -57,6 +57,10 @@ class DQNAgent:
             init_val=config.init_random_action_prob,
             min_val=config.min_random_action_prob,
             steps=config.random_action_explore_steps)
+        if getattr(config, 'augment', 'none') == 'shift' and not network.arch.is_conv:
+            raise ValueError('--augment shift needs image observations and a convolutional network, got '
+                             'network=%s on observations of shape %s'
+                             % (network.arch.network, tuple(network.arch.input_shape)))
         if session is None:
             from .learner import Learner
             session = Learner(network, replay_memory, config) if isinstance(replay_memory, DeviceReplay) else None
@@ -199,6 +203,15 @@ class DQNAgent:
             dev = self.network.device
             tb = {k: torch.from_numpy(v).to(dev) for k, v in batch.items()}
             tb['gammas'] = torch.full_like(tb['rewards'], self.config.reward_discount ** self.config.n_step)
+            if getattr(self.config, 'augment', 'none') == 'shift':
+                # host replay: the same random shift as the device learner's (ops/augment.py)
+                from .ops import augment
+                if tb['states'].dim() != 4:
+                    raise ValueError('--augment shift needs image observations, got states of shape %s'
+                                     % (tuple(tb['states'].shape),))
+                tb['states'], tb['next_states'], _ = augment.shift_stacks(
+                    tb['states'], tb['next_states'], augment.aug_seed(self.config.seed),
+                    self.network.global_step, self.config.aug_pad)
             loss, _ = self.network.train_step(tb)
         self.sgd_meter.add(1)
         if self._should_log_summary():

@@ -135,6 +135,15 @@ def build_parser() -> argparse.ArgumentParser:
            'clip_by_global_norm: g *= C / max(||g||, C), after the data-parallel average; the decoupled L2 '
            'term stays unclipped; a non-finite norm applies no gradient). 0 = off. A clipped run gives up '
            'the fused weight-gradient / update launches (--fuse_fc_wgrad, --fuse_wgrad_update, --det_wgrad)')
+    a('--augment', default='none', choices=['none', 'shift'],
+      help='Learner-side frame augmentation. shift = DrQ random shift (Kostrikov et al. 2020; DrQ-eps, '
+           'data-efficient Rainbow, SPR, BBF): every sampled stack is replicate-padded by --aug_pad pixels and '
+           'cropped back at a random offset, drawn per sample and per SGD step, independently for s and s\'; '
+           'acting and evaluation see the frames unshifted. Image observations only. On the HIP path one '
+           'gather launch per step (csrc/kernels/augment.hip) writes the shifted stacks from the replay frame '
+           'ring and conv1 / its weight gradient read those instead of the ring; the trunk\'s in-kernel '
+           'sampling (--fuse_sampling=1) is not available')
+    a('--aug_pad', default=4, type=int, help='--augment shift: pad / maximum shift in pixels (1..16)')
     a('--noisy', action='store_true', help='Factorised-Gaussian noisy FC layers')
     a('--noisy_sigma0', default=0.5, type=float)
     a('--target_update_tau', default=1.0, type=float,
@@ -195,7 +204,10 @@ def build_parser() -> argparse.ArgumentParser:
     a('--hip_graph', default=1, type=int, help='Capture the learner step in a HIP graph')
     a('--fuse_sampling', default=2, type=int, choices=[0, 1, 2],
       help='Uniform GPU replay: 0 = sampler launch per step, 1 = the Nature trunk draws the minibatch, '
-           '2 = the previous step\'s optimizer launch draws it (one extra block, off the critical path)')
+           '2 = the previous step\'s optimizer launch draws it (one extra block, off the critical path). '
+           '1 reads the frame ring inside the trunk, so it cannot be combined with --augment shift, whose '
+           'shifted stacks must exist before the trunk starts (an augmented run that would resolve to the '
+           'trunk\'s sampling uses a sampler launch)')
     a('--summary_secs', default=120.0, type=float,
       help='chief: seconds between global_step/sec summaries (TF Supervisor step counter: 120)')
     a('--ps_timeout_s', default=60.0, type=float,
@@ -306,6 +318,8 @@ class Config:
     m_tau: float = 0.03
     m_clip: float = -1.0
     max_grad_norm: float = 0.0
+    augment: str = 'none'
+    aug_pad: int = 4
     noisy: bool = False
     noisy_sigma0: float = 0.5
     target_update_tau: float = 1.0
@@ -396,6 +410,14 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> Config:
     if ns.max_grad_norm > 0.0 and ns.async_ps:
         p.error('--max_grad_norm and --async_ps cannot be combined: the parameter server applies the workers\' '
                 'pushes in arrival order, so the clip belongs on the server, which does not clip')
+    if not 1 <= ns.aug_pad <= 16:
+        p.error('--aug_pad must lie in 1..16, got %d' % ns.aug_pad)
+    if ns.augment == 'shift':
+        if ns.network == 'simple':
+            p.error('--augment shift needs image observations: the simple (MLP) network takes vector observations')
+        if ns.fuse_sampling == 1:
+            p.error('--augment shift and --fuse_sampling=1 cannot be combined: the trunk would draw the minibatch '
+                    'after the shifted stacks are needed (use --fuse_sampling=2, the default, or 0)')
     return Config.from_namespace(ns)
 
 

@@ -176,6 +176,22 @@ class Learner:
             self._ar_ranges = []           # (nothing left for an all-reduce launch)
         if hasattr(ex, 'dp_exchange'):
             ex.dp_exchange = self.reducer.xgmi if self._dp_fused else None
+        # --augment shift: every sampled stack randomly shifted (ops/augment.py), drawn from
+        # (seed, global_step, b, which). Slot batches go through one gather launch into persistent stacks
+        # (augment.hip) and the executor reads those, never the frame ring; gathered stacks are shifted
+        # by the same function in torch
+        self._augment = getattr(config, 'augment', 'none') == 'shift'
+        self.aug_shifts = None         # int32 [B, 2, 2]: the last step's (dy, dx) of s and s' (device)
+        if self._augment:
+            from .ops import augment
+            if not (getattr(replay, 'frame_mode', False) and network.arch.is_conv):
+                raise ValueError('--augment shift needs image observations (a frame-stacked replay and a '
+                                 'convolutional network), got network=%s' % network.arch.network)
+            self._aug_pad = augment.check_pad(config.aug_pad)
+            self._aug_seed = augment.aug_seed(getattr(config, 'seed', None), self.ctx.rank)
+            self._aug_bufs = {}
+            self._aug_calls = 0
+            self.aug_shift_log = None
         self.train_steps = 0           # reference DQNAgent.training_steps (host-side mirror)
         if use_graph is None:
             use_graph = bool(config.hip_graph) and self.device.type == 'cuda'
@@ -225,6 +241,8 @@ class Learner:
             else:
                 batch = r.sample_slots(self.B, beta, defer=mode == 'trunk')
             self.idx = batch['idx']
+            if self._augment:
+                batch = self._shifted_batch(batch)
         else:
             if per:
                 r.sample_prioritized(self.B, beta, self.idx, self.weights)
@@ -233,6 +251,11 @@ class Learner:
             batch = r.gather(self.idx)
             if per:
                 batch['weights'] = self.weights
+            if self._augment:
+                from .ops import augment
+                batch['states'], batch['next_states'], sh = augment.shift_stacks(
+                    batch['states'], batch['next_states'], self._aug_seed, self.net.global_step, self._aug_pad)
+                self.aug_shifts = sh.to(torch.int32)
         self.net.begin_step_noise()
         acting = None
         if self.actor is not None:
@@ -252,9 +275,38 @@ class Learner:
         self.loss = loss.view(1)
         self.prio = prio.view(-1)
 
+    def _shifted_batch(self, batch: dict) -> dict:
+        """--augment shift on a slot batch: ONE launch gathers both randomly shifted stacks from the
+        frame ring into persistent per-B buffers (graph-safe; the shifts follow the device global_step,
+        so every step of a multi-step graph draws its own). The executor gets the stacks as ``states`` /
+        ``next_states``; ``frames`` stays in the batch only for a fused actor instance, which reads the
+        ring unshifted through its own slot table.
+
+        The drawn (dy, dx) pairs go to ``aug_shift_log`` [8, B, 2, 2], one row per step body in
+        rotation (the row is fixed when a body is captured, so a graph of k <= 8 steps leaves its k
+        shift sets in k rows); ``aug_shifts`` is the row of the last body run or captured."""
+        r = self.replay
+        buf = self._aug_bufs.get(self.B)
+        if buf is None:
+            H, W = r.obs_shape
+            u8 = dict(dtype=torch.uint8, device=self.device)
+            buf = self._aug_bufs[self.B] = (torch.zeros(self.B, H, W, r.k, **u8), torch.zeros(self.B, H, W, r.k, **u8),
+                                            torch.zeros(8, self.B, 2, 2, dtype=torch.int32, device=self.device))
+        s, ns, self.aug_shift_log = buf
+        self.aug_shifts = self.aug_shift_log[self._aug_calls % 8]
+        self._aug_calls += 1
+        kernels.replay_gather_shift(batch['frames'], batch['state_slots'], batch['next_slots'], self._aug_seed,
+                                    self.net.global_step, self._aug_pad, s, ns, self.aug_shifts)
+        out = {k: v for k, v in batch.items() if k not in ('state_slots', 'next_slots', 'frames', 'sample_spec')}
+        out['states'], out['next_states'] = s, ns
+        if self.actor is not None:
+            out['frames'] = batch['frames']
+        return out
+
     def _sample_mode(self) -> str:
         """Where the uniform minibatch is drawn: 'opt' (an extra block of the previous step's
-        optimizer launch), 'trunk' (the Nature trunk launch) or 'launch' (a sampler launch)."""
+        optimizer launch), 'trunk' (the Nature trunk launch) or 'launch' (a sampler launch).
+        --augment shift: never 'trunk' (the shifted stacks are gathered before the trunk starts)."""
         r = self.replay
         fs = int(getattr(self.config, 'fuse_sampling', 2))
         if (fs >= 2 and self.ps is None and getattr(r, 'can_fuse_sampling', lambda B: False)(self.B)
@@ -263,7 +315,7 @@ class Learner:
             return 'opt'            # (prioritized too: priority update + sample in that block)
         if getattr(r, 'prioritized', False) or not getattr(r, 'can_defer_sampling', lambda: False)():
             return 'launch'
-        if fs >= 1 and getattr(self.net.executor, 'fused_sampling', False):
+        if fs >= 1 and getattr(self.net.executor, 'fused_sampling', False) and not self._augment:
             return 'trunk'
         return 'launch'
 

@@ -938,7 +938,8 @@ class HipExecutor:
         ``_fc_fwd``.
 
         xs: uint8 NHWC [B, 84, 84, 4] inputs, or (frames given) int32 [B, 4] slot
-        tables into the frame ring ``frames`` [F, 84, 84] (fused gather)."""
+        tables into the frame ring ``frames`` [F, 84, 84] (fused gather). With ``frames``
+        the fused trunk takes either kind per instance (``_input_ptrs``)."""
         ext, lay = self.ext, self.layout
         c1, c2, c3 = self.arch.convs
         (h1, w1), (h2, w2), (h3, w3) = c1.out_hw, c2.out_hw, c3.out_hw
@@ -948,8 +949,7 @@ class HipExecutor:
         if self.fused_trunk:
             # ONE launch for conv1..conv3: a workgroup per (sample, instance), activations in LDS
             pad = lambda v: list(v) + [0] * (4 - len(v))
-            slots = [x.data_ptr() for x in xs] if frames is not None else []
-            states = [] if frames is not None else [x.data_ptr() for x in xs]
+            slots, states = self._input_ptrs(xs, frames)
             ptrs = (pad(slots) + pad(states) + pad(pk('conv1/fwd')) + pad(pk('conv2/fwd')) + pad(pk('conv3/fwd'))
                     + pad(bias('conv1/b')) + pad(bias('conv2/b')) + pad(bias('conv3/b'))
                     # only the online(s) instance feeds the backward: the others skip x1/x2
@@ -965,6 +965,8 @@ class HipExecutor:
         d1 = [B * h1 * w1, c1.cout, c1.k * c1.k * c1.cin, (c1.cout + 15) // 16, c1.cout, 84, 84, h1, w1, 0, 0]
         kind1 = _KIND['C1']
         if frames is not None:
+            # (one loader per launch: ``supports_mixed_inputs``)
+            assert all(x.dtype == torch.int32 for x in xs), 'layer-wise convs: slot tables or stacks, not both'
             d1 += [frames.data_ptr(), 84 * 84]
             kind1 = _KIND['F1']
         ext.qnet_igemm(kind1, [x.data_ptr() for x in xs], pk('conv1/fwd'), bias('conv1/b'),
@@ -1066,6 +1068,23 @@ class HipExecutor:
             b = [off(f, 'output/b') for f in flats]
             wv, bv = [], []
         return w, b, wv, bv
+
+    @staticmethod
+    def _input_ptrs(xs, frames):
+        """Per-instance (slot-table pointers, stack pointers) of a fused forward launch, 0 = the other
+        kind: with the frame ring an int32 x is a [B, 4] slot table into it and a uint8 x an NHWC
+        stack (the kernels select per instance); without it every x is a stack."""
+        if frames is None:
+            return [], [x.data_ptr() for x in xs]
+        tab = [x.dtype == torch.int32 for x in xs]
+        return ([x.data_ptr() if t else 0 for x, t in zip(xs, tab)],
+                [0 if t else x.data_ptr() for x, t in zip(xs, tab)])
+
+    def supports_mixed_inputs(self) -> bool:
+        """Whether one step can read its learner instances from uint8 stacks (``--augment shift``)
+        and a fused actor instance from the frame ring: the fused forward kernels choose the loader
+        per instance, the layer-wise convs take one loader per launch."""
+        return bool(self.fused_trunk)
 
     def _check_states(self, x):
         assert x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape[1:]) == (84, 84, 4), \
@@ -1275,7 +1294,12 @@ class HipExecutor:
         also draws the next noise samples from the device stream ``rng`` into out0 / out1 (no
         launch of its own); ``update_and_pack(noise_rng=rng)`` then advances the stream.
 
-        acting (fused acting, slot batches only): {'stacks': [E, 4] int32 frame slots of the
+        batch: slot tables (``state_slots`` / ``next_slots`` + the frame ring ``frames``: conv1 and its
+        weight gradient read the ring) or uint8 stacks (``states`` / ``next_states``: gathered, or the
+        randomly shifted ones of ``--augment shift``; both then read the stacks, never the ring). A batch
+        of stacks may still carry ``frames`` for a fused actor instance (``supports_mixed_inputs``).
+
+        acting (fused acting; the batch carries ``frames``): {'stacks': [E, 4] int32 frame slots of the
         device actors' states, 'ptrs', 'ints', 'f': the actor-step arguments of act_fused}. The
         actors' states ride along as one more trunk / fc instance with the online weights, and
         one extra workgroup of the head launch runs the eps-greedy / env / replay-append step:
@@ -1320,15 +1344,24 @@ class HipExecutor:
     def _begin_step(self, online, target, batch, grad_out, noise, noise_target, acting) -> SimpleNamespace:
         """Batch checks, workspace, packed / effective weights: the step's tensors and pointers."""
         lay = self.layout
-        frames = batch.get('frames')
-        if frames is not None:             # slot batch: conv1 reads the replay frame ring directly
-            s, ns = batch['state_slots'], batch['next_slots']
-            assert s.dtype == torch.int32 and s.shape[1] == 4 and s.is_contiguous() and ns.is_contiguous()
-            assert frames.dtype == torch.uint8 and tuple(frames.shape[1:]) == (84, 84)
-        else:
+        # ring: the replay frame ring, for the instances that read it through slot tables (the learner's
+        # of a slot batch; a fused actor's always). frames: the ring when the LEARNER instances read it
+        # -- None for a batch of uint8 stacks (gathered, or shifted by --augment shift), whose conv1
+        # forward and weight gradient then take the stack loaders and never touch the ring
+        ring = batch.get('frames')
+        if ring is not None:
+            assert ring.dtype == torch.uint8 and tuple(ring.shape[1:]) == (84, 84)
+        if 'states' in batch:
+            assert 'state_slots' not in batch, 'a batch is either stacks or slot tables'
+            frames = None
             s, ns = batch['states'], batch['next_states']
             self._check_states(s)
             self._check_states(ns)
+        else:                              # slot batch: conv1 reads the replay frame ring directly
+            frames = ring
+            assert frames is not None, 'a slot batch carries the frame ring'
+            s, ns = batch['state_slots'], batch['next_slots']
+            assert s.dtype == torch.int32 and s.shape[1] == 4 and s.is_contiguous() and ns.is_contiguous()
         B = s.shape[0]
         assert B <= 1024
         dev = s.device
@@ -1339,7 +1372,9 @@ class HipExecutor:
         ninst = 3 if self.double or self.mdqn is not None else 2
         E = 0
         if acting is not None:
-            assert frames is not None and self.supports_fused_acting(), 'fused acting needs a slot batch'
+            assert ring is not None and self.supports_fused_acting(), 'fused acting needs the frame ring'
+            assert frames is not None or self.supports_mixed_inputs(), \
+                'fused acting beside a batch of stacks needs the fused forward (per-instance loaders)'
             E = acting['stacks'].shape[0]
             assert acting['stacks'].dtype == torch.int32 and acting['stacks'].is_contiguous() and E <= B
         spec = batch.get('sample_spec')
@@ -1351,7 +1386,8 @@ class HipExecutor:
         if self.mdqn is not None:          # the third instance: the target net on the sampled states
             xs, packs, flats = [s, ns, s], [po, pt, pt], [eo, et, et]
         return SimpleNamespace(
-            B=B, dev=dev, ws=ws, s=s, frames=frames, po=po, eo=eo, ninst=ninst, acting=acting, E=E, grad=grad_out,
+            B=B, dev=dev, ws=ws, s=s, frames=frames, ring=ring, po=po, eo=eo, ninst=ninst, acting=acting, E=E,
+            grad=grad_out,
             xs=xs[:ninst], packs=packs[:ninst], flats=flats[:ninst],
             sample=(spec, ninst) if spec is not None else None, fold=self.can_fold_head(B, E),
             g=lambda n: grad_out.data_ptr() + 4 * lay.offsets[n],
@@ -1383,8 +1419,9 @@ class HipExecutor:
             self._fwd_trunk(st.xs, st.packs, st.flats, st.ws, B, st.ninst, frames=st.frames, sample=st.sample,
                             fc=not st.fold, fc_zero=st.fc_zero)
         else:
+            # (the actor instance reads the ring through its slot table whatever the learner instances read)
             self._fwd_trunk(st.xs + [st.acting['stacks']], st.packs + [st.po], st.flats + [st.eo], st.ws, B,
-                            st.ninst + 1, frames=st.frames, M=[B] * st.ninst + [st.E], sample=st.sample,
+                            st.ninst + 1, frames=st.ring, M=[B] * st.ninst + [st.E], sample=st.sample,
                             fc=not st.fold, fc_zero=st.fc_zero)
         if not fl.zero_in_head:
             st.main.wait_event(ev_zero)
@@ -1618,6 +1655,9 @@ class HipCnnExecutor(HipExecutor):
 
     fused_sampling = False          # cnn.hip's forward reads sampler-made slot tables
 
+    def supports_mixed_inputs(self) -> bool:
+        return True                 # (cnn_fwd_kernel chooses the loader per instance)
+
     def _workspace(self, B: int, dev) -> dict:
         key = (B, dev.index if dev.index is not None else 0)
         ws = self._ws.get(key)
@@ -1648,8 +1688,7 @@ class HipCnnExecutor(HipExecutor):
         pad = lambda v: list(v) + [0] * (4 - len(v))
         pk = lambda key: [p.data_ptr() + self.esz * self.poff[key] for p in packs]
         bias = lambda name: [f.data_ptr() + 4 * lay.offsets[name] for f in flats]
-        slots = [x.data_ptr() for x in xs] if frames is not None else []
-        states = [] if frames is not None else [x.data_ptr() for x in xs]
+        slots, states = self._input_ptrs(xs, frames)
         keep = [ws[k].data_ptr() for k in ('a1', 'p1', 'a2', 'p2', 'a3')] if keep_acts else [0] * 5
         ptrs = (pad(slots) + pad(states) + pad(pk('conv1/fwd')) + pad(pk('conv2/fwd')) + pad(pk('conv3/fwd'))
                 + pad(bias('conv1/b')) + pad(bias('conv2/b')) + pad(bias('conv3/b'))

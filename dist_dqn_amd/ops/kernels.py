@@ -77,6 +77,40 @@ def replay_gather_frames(frames: torch.Tensor, state_idx: torch.Tensor, next_idx
     return s, ns
 
 
+def replay_gather_shift(frames: torch.Tensor, state_slots: torch.Tensor, next_slots: torch.Tensor, seed: int,
+                        ctr: torch.Tensor, pad: int, out_s: Optional[torch.Tensor] = None,
+                        out_ns: Optional[torch.Tensor] = None, shifts_out: Optional[torch.Tensor] = None,
+                        ext=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Randomly shifted uint8 NHWC stacks of a sampled minibatch (``--augment shift``; semantics:
+    ``ops/augment.py``): out_s / out_ns [B, H, W, 4] gathered from the frame ring through the
+    [B, 4] int32 slot tables a sampler wrote, each stack replicate-padded by ``pad`` and cropped at
+    the (dy, dx) drawn for (``seed``, ``ctr``, b, which); shifts_out int32 [B, 2, 2] receives the
+    drawn pairs. ``ctr``: one-element int64 tensor read by the kernel (the learner's global_step).
+    ``pad`` = 0 is the plain gather. GPU: one HIP launch (csrc/kernels/augment.hip), graph-safe
+    when the outputs are given; CPU: the torch reference."""
+    from . import augment
+    pad = augment.check_pad(pad)
+    B, k = state_slots.shape
+    H, W = frames.shape[1], frames.shape[2]
+    dev = frames.device
+    if out_s is None:
+        out_s = torch.empty(B, H, W, k, dtype=torch.uint8, device=dev)
+    if out_ns is None:
+        out_ns = torch.empty(B, H, W, k, dtype=torch.uint8, device=dev)
+    if shifts_out is None:
+        shifts_out = torch.zeros(B, 2, 2, dtype=torch.int32, device=dev)
+    if frames.is_cuda:
+        ext = ext if ext is not None else _ext.load(required=True)
+        ext.replay_gather_shift(frames, state_slots, next_slots, int(seed), ctr, pad, out_s, out_ns, shifts_out)
+        return out_s, out_ns, shifts_out
+    stack = lambda sl: frames.index_select(0, sl.reshape(-1).long()).view(B, k, H, W).permute(0, 2, 3, 1)
+    s, ns, sh = augment.shift_stacks(stack(state_slots), stack(next_slots), seed, ctr, pad)
+    out_s.copy_(s)
+    out_ns.copy_(ns)
+    shifts_out.copy_(sh.to(torch.int32))
+    return out_s, out_ns, shifts_out
+
+
 # -------------------------------------------------------------- sum-tree ops
 def sumtree_set(tree, idx: torch.Tensor, td_abs: Optional[torch.Tensor], alpha: float, eps: float,
                 use_max: bool):
