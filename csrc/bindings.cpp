@@ -460,7 +460,9 @@ void preprocess_host(torch::Tensor in, torch::Tensor out) {
 void actor_step(torch::Tensor q, torch::Tensor frames, torch::Tensor stacks, torch::Tensor cursor,
                 torch::Tensor size_dev, torch::Tensor state_idx, torch::Tensor next_idx, torch::Tensor actions,
                 torch::Tensor rewards, torch::Tensor dones, torch::Tensor gammas, torch::Tensor eps, torch::Tensor rng,
-                torch::Tensor ticket, torch::Tensor frames_done, double gamma, double p_done) {
+                torch::Tensor ticket, torch::Tensor frames_done, double gamma, double p_done,
+                std::vector<torch::Tensor> tree) {
+  // tree: [] or the prioritized replay's [sum, min, max_p]: the E new transitions enter at max priority
   CHECK_T(q, torch::kFloat32); CHECK_T(frames, torch::kUInt8); CHECK_T(stacks, torch::kInt32);
   CHECK_T(cursor, torch::kInt64); CHECK_T(size_dev, torch::kInt32); CHECK_T(state_idx, torch::kInt32);
   CHECK_T(next_idx, torch::kInt32); CHECK_T(actions, torch::kInt32); CHECK_T(rewards, torch::kFloat32);
@@ -471,14 +473,32 @@ void actor_step(torch::Tensor q, torch::Tensor frames, torch::Tensor stacks, tor
   TORCH_CHECK(stacks.size(0) == E && state_idx.size(1) == K, "stack shapes");
   TORCH_CHECK(K >= 1 && K <= 4, "actor: frames_per_state must be 1..4");
   TORCH_CHECK(cursor.numel() == 3 && eps.numel() == 3 && rng.numel() == 2, "state vectors");
-  TORCH_CHECK(F >= 2 * C + K, "frame ring must hold 2C + k frames");
+  TORCH_CHECK(size_dev.numel() >= 1 && ticket.numel() >= 1 && frames_done.numel() >= 1, "state scalars");
+  TORCH_CHECK(next_idx.numel() == C && actions.numel() == C && rewards.numel() == C && dones.numel() == C &&
+              gammas.numel() == C, "replay columns must be [C]");
   TORCH_CHECK(E >= 1 && E <= C, "env count");
+  // a stack reaches k steps = 2kE frame slots back while its transition lives (replay/device.py)
+  TORCH_CHECK((int64_t)F >= 2 * (int64_t)C + 2 * (int64_t)K * E,
+              "frame ring must hold 2C + 2kE frames for E device envs (DeviceReplay.reserve_writers)");
+  float *tsum = nullptr, *tmin = nullptr, *tmaxp = nullptr;
+  int tP = 0, tlevels = 0;
+  if (!tree.empty()) {
+    TORCH_CHECK(tree.size() == 3, "tree = [sum, min, max_p]");
+    for (auto& t : tree) { CHECK_T(t, torch::kFloat32); }
+    TORCH_CHECK(E <= 64, "actor: the prioritized insertion takes at most 64 envs per step");
+    const int64_t P2 = tree[0].numel();
+    TORCH_CHECK(P2 >= 2 && (P2 & (P2 - 1)) == 0 && tree[1].numel() == P2 && tree[2].numel() >= 1 && P2 / 2 >= C &&
+                P2 <= (int64_t(1) << 31), "actor PER tree: sum / min of 2P entries, P = 2^levels >= capacity");
+    tP = (int)(P2 / 2);
+    while ((1 << tlevels) < tP) ++tlevels;
+    tsum = ptr<float>(tree[0]); tmin = ptr<float>(tree[1]); tmaxp = ptr<float>(tree[2]);
+  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
   launch_actor_step(ptr<float>(q), ptr<uint8_t>(frames), ptr<int32_t>(stacks), ptr<int64_t>(cursor),
                     ptr<int32_t>(size_dev), ptr<int32_t>(state_idx), ptr<int32_t>(next_idx), ptr<int32_t>(actions),
                     ptr<float>(rewards), ptr<float>(dones), ptr<float>(gammas), ptr<float>(eps), ptr<int64_t>(rng),
                     ptr<int32_t>(ticket), ptr<int64_t>(frames_done), E, A, K, HW, C, F, (float)gamma, (float)p_done,
-                    cur_stream());
+                    tsum, tmin, tmaxp, tP, tlevels, cur_stream());
 }
 
 void stack_states(torch::Tensor frames, torch::Tensor stacks, torch::Tensor out) {
@@ -885,7 +905,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("td_loss_c51", &td_loss_c51);
   m.def("preprocess_batch", &preprocess_batch);
   m.def("preprocess_host", &preprocess_host);
-  m.def("actor_step", &actor_step);
+  m.def("actor_step", &actor_step, pybind11::arg("q"), pybind11::arg("frames"), pybind11::arg("stacks"),
+        pybind11::arg("cursor"), pybind11::arg("size_dev"), pybind11::arg("state_idx"), pybind11::arg("next_idx"),
+        pybind11::arg("actions"), pybind11::arg("rewards"), pybind11::arg("dones"), pybind11::arg("gammas"),
+        pybind11::arg("eps"), pybind11::arg("rng"), pybind11::arg("ticket"), pybind11::arg("frames_done"),
+        pybind11::arg("gamma"), pybind11::arg("p_done"), pybind11::arg("tree") = std::vector<torch::Tensor>{});
   m.def("stack_states", &stack_states);
   m.def("crc32c", &crc32c);
   m.def("ring_bytes", [](int64_t cap, int64_t rec) { return (int64_t)dqn_ring_bytes(cap, rec); });

@@ -138,7 +138,8 @@ void launch_preprocess_batch(const uint8_t* in, uint8_t* out, int N, int Hs, int
 void launch_actor_step(const float* q, uint8_t* frames, int32_t* stacks, int64_t* cursor, int32_t* size_dev,
                        int32_t* state_idx, int32_t* next_idx, int32_t* actions, float* rewards, float* dones,
                        float* gammas, float* eps, int64_t* rng, int32_t* ticket, int64_t* frames_done, int E,
-                       int A, int K, int HW, int C, int F, float gamma, float p_done, hipStream_t st);
+                       int A, int K, int HW, int C, int F, float gamma, float p_done, float* tsum, float* tmin,
+                       float* tmaxp, int tP, int tlevels, hipStream_t st);   // tsum: PER tree, or nullptr
 void launch_stack_states(const uint8_t* frames, const int32_t* stacks, uint8_t* out, int E, int HW, int K,
                          hipStream_t st);
 

@@ -11,8 +11,11 @@
 //
 // Replay cursor (device-resident): cursor[0] = next transition slot,
 // cursor[1] = next frame slot, cursor[2] = size. Each call consumes E
-// transition slots and 2E frame slots (next frame + a reserved reset frame),
-// matching the replay's frame-ring bound F >= 2C + k. The LAST block to finish
+// transition slots and 2E frame slots (next frame + a reserved reset frame).
+// A state stack reaches k steps = 2kE slots back while its transition lives
+// for C more transitions = up to 2C more slots, so the frame ring needs
+// F >= 2C + 2kE (derived in replay/device.py; the bindings check it, and
+// DeviceReplay.reserve_writers allocates it). The LAST block to finish
 // advances the cursor, the epsilon state and the RNG counter (arrival ticket).
 #include "actor_dev.h"
 #include "../include/dqn_kernels.h"
@@ -69,9 +72,10 @@ using namespace dqn;
 void launch_actor_step(const float* q, uint8_t* frames, int32_t* stacks, int64_t* cursor, int32_t* size_dev,
                        int32_t* state_idx, int32_t* next_idx, int32_t* actions, float* rewards, float* dones,
                        float* gammas, float* eps, int64_t* rng, int32_t* ticket, int64_t* frames_done, int E,
-                       int A, int K, int HW, int C, int F, float gamma, float p_done, hipStream_t st) {
+                       int A, int K, int HW, int C, int F, float gamma, float p_done, float* tsum, float* tmin,
+                       float* tmaxp, int tP, int tlevels, hipStream_t st) {
   ActorArgs a{q, frames, stacks, cursor, size_dev, state_idx, next_idx, actions, rewards, dones, gammas,
-              eps, rng, ticket, frames_done, E, A, K, HW, C, F, gamma, p_done};
+              eps, rng, ticket, frames_done, E, A, K, HW, C, F, gamma, p_done, tsum, tmin, tmaxp, tP, tlevels};
   hipLaunchKernelGGL(actor_step_kernel, dim3(E), dim3(256), 0, st, a);
 }
 

@@ -174,8 +174,10 @@ dqn::HeadArgs head_args(const std::vector<int64_t>& ints, const std::vector<int6
                   "actor PER tree: P = 2^levels >= capacity");
     }
     TORCH_CHECK(x.A == a.A, "actor action count");
-    TORCH_CHECK(x.F >= 2 * x.C + x.K, "frame ring must hold 2C + k frames");
     TORCH_CHECK(x.K >= 1 && x.K <= 4 && x.E >= 1 && x.E <= 64, "fused actor: 1 <= K <= 4, 1 <= E <= 64");
+    // a stack reaches k steps = 2kE frame slots back while its transition lives (replay/device.py)
+    TORCH_CHECK((int64_t)x.F >= 2 * (int64_t)x.C + 2 * (int64_t)x.K * x.E,
+                "frame ring must hold 2C + 2kE frames for E device envs (DeviceReplay.reserve_writers)");
     if (a.infer) {                 // acting launch: the batch IS the env batch
       TORCH_CHECK(x.E == a.B, "actor env batch must be the inference batch");
       a.has_actor = 1;

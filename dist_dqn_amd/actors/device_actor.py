@@ -31,8 +31,11 @@ class DeviceActor:
         k = replay.k
         H, W = replay.obs_shape
         self.ext = _ext.load(required=True)
-        # start every env on a fresh random reset frame
+        # E envs take 2E frame slots per step: the ring must be sized for them (replay/device.py),
+        # before anything below or any learner keeps the address of `frames`
         r = replay
+        r.reserve_writers(num_envs)
+        # start every env on a fresh random reset frame
         base = r._f_next
         slots = (torch.arange(num_envs, device=dev) + base) % r.num_frames
         r.frames[slots.long()] = torch.randint(0, 256, (num_envs, H, W), dtype=torch.uint8, device=dev)
@@ -102,7 +105,8 @@ class DeviceActor:
         q = self.net.q_values(self.states).float().contiguous()
         self.ext.actor_step(q, r.frames, self.stacks, r.cursor, r.size_dev, r.state_idx, r.next_idx, r.actions,
                             r.rewards, r.dones, r.gammas, self.eps, self.rng, self.ticket, self.frames_done,
-                            self.gamma, self.p_done)
+                            self.gamma, self.p_done,
+                            tree=[r.tree.sum, r.tree.min, r.tree.max_p] if r.prioritized else [])
 
     def _body(self):
         for _ in range(self.steps):

@@ -16,8 +16,30 @@ Here the replay is a set of device tensors:
     (gammas = gamma^n of the stored n-step transition).
 Vector observations (CartPole) are stored directly as f32 [C, D] twice.
 
-Frame ring size F = 2C + k + 8: every transition writes one frame and at most
-one reset frame, so a valid transition's frames are never overwritten.
+Frame ring size (``frame_ring_size``). A host-fed replay allocates frame slots
+one at a time: a transition takes one new frame and at most one reset frame, and
+its oldest state frame is at most k - 1 frames older, so F = 2C + k + 8 keeps a
+live transition's frames from being overwritten.
+
+Device actors (``DeviceActor``: E envs written by one kernel launch per step)
+take frame slots 2E at a time: env e of a step at frame cursor f uses slots
+f + 2e and f + 2e + 1, and the cursor moves on by 2E. Count slots from the
+ring's start without wrapping. The transition env e writes in step s is the
+(E s + e)-th; it stays live until C more were written, that is through step
+s + floor((C + e) / E) - 1, after which the cursor stands at
+2E (s + floor((C + e) / E)) <= 2E s + 2 (C + e). The oldest frame of its state
+stack was written k steps before it, at 2E (s - k) + 2e (a younger stack, after
+a reset, only starts later). That slot is reused once the cursor has moved F
+past it, so the transition's frames survive it when
+
+    2E s + 2 (C + e) - (2E (s - k) + 2e) = 2C + 2 k E <= F.
+
+The bound is tight (take e with E | C + e), and it is 2kE, not k, above 2C:
+with E > 1 the ring of a host-fed replay is too small, a live transition's
+oldest frames are overwritten by frames from its future. ``reserve_writers(E)``
+grows the ring to F = 2C + 2kE + k + 8 (``DeviceActor`` calls it); the bindings
+refuse a device actor step on a smaller ring than 2C + 2kE.
+(``tests/actor_ref.py`` models the rings; its ``stale()`` is the check.)
 1M transitions = 14 GB of frames — 5% of one MI355X's 288 GB HBM — so the
 default capacity per GPU can be far larger than the reference's.
 
@@ -89,7 +111,7 @@ class DeviceReplay:
         dev = self.device
         if self.frame_mode:
             H, W = self.obs_shape
-            self.num_frames = 2 * C + self.k + 8
+            self.num_frames = self.frame_ring_size(C, self.k)
             self.frames = torch.zeros(self.num_frames, H, W, dtype=torch.uint8, device=dev)
             self.state_idx = torch.zeros(C, self.k, dtype=torch.int32, device=dev)
             self.next_idx = torch.zeros(C, dtype=torch.int32, device=dev)
@@ -126,6 +148,27 @@ class DeviceReplay:
         # device-side writers (DeviceActor) keep [t_next, f_next, size] on the GPU
         self.cursor = None
         self.device_writer = False
+
+    # ------------------------------------------------------- frame ring size
+    @staticmethod
+    def frame_ring_size(capacity: int, k: int, writers: int = 0) -> int:
+        """Frames in the ring of a replay of ``capacity`` transitions with k-frame states:
+        host-fed (writers = 0), or written by ``writers`` device envs per step (module docstring)."""
+        return 2 * capacity + 2 * k * max(0, int(writers)) + k + 8
+
+    def reserve_writers(self, num_envs: int):
+        """Make the frame ring large enough for ``num_envs`` device envs per step, keeping its
+        contents. Reallocates ``frames``: call it before anything keeps ``frames.data_ptr()``
+        (a captured graph, an argument list) -- ``DeviceActor`` does, when it is built."""
+        assert self.frame_mode
+        need = self.frame_ring_size(self.capacity, self.k, num_envs)
+        if need <= self.num_frames:
+            return
+        assert not (self._stage.nf or self._stage.nt), 'flush() staged frames before the ring grows'
+        old = self.frames
+        self.frames = torch.zeros(need, old.shape[1], old.shape[2], dtype=torch.uint8, device=self.device)
+        self.frames[:old.shape[0]].copy_(old)
+        self.num_frames = need
 
     # ----------------------------------------------------------- staging
     def _reset_stage(self):
