@@ -289,19 +289,15 @@ int launch_fc_head(const dqn::ConvArgs& a, const dqn::HeadArgs& h, const dqn::Fo
 void launch_trunk_fwd(const dqn::TrunkArgs& a, int B, int ninst, hipStream_t st);
 void launch_c51_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t c51_head_lds_bytes(const dqn::HeadArgs& a);
-int c51_train_blocks(const dqn::HeadArgs& a);     // learner blocks = loss partials of the training head
 // QR-DQN head (qr_head.hip): HeadArgs::atoms = quantiles per action, HeadArgs::delta = kappa
 void launch_qr_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t qr_head_lds_bytes(const dqn::HeadArgs& a);
-int qr_train_blocks(const dqn::HeadArgs& a);
 // Wide QR-DQN head (qr_wide_head.hip): 64 < quantiles <= 256, % 4 == 0; same arguments and outputs
 void launch_qr_wide_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t qr_wide_head_lds_bytes(const dqn::HeadArgs& a);
-int qr_wide_train_blocks(const dqn::HeadArgs& a);  // learner blocks = loss partials: min(B, 64)
 // Munchausen-DQN head (mdqn_head.hip): HeadArgs::m_alpha / m_tau / m_clip, Huber threshold in delta
 void launch_mdqn_head(const dqn::HeadArgs& a, hipStream_t st);
 size_t mdqn_head_lds_bytes(const dqn::HeadArgs& a);
-int mdqn_train_blocks(const dqn::HeadArgs& a);
 void launch_noisy_mix(const float* flat, float* eff, const float* noise, const dqn::NoisyJob* jobs, int njobs,
                       int max_elems, hipStream_t st);
 void launch_noisy_grad(float* grad, const float* noise, const dqn::NoisyJob* jobs, int njobs, int max_elems,

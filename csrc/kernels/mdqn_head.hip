@@ -195,8 +195,6 @@ size_t mdqn_head_lds_bytes(const HeadArgs& a) {
   return mdqn_infer_q_bytes(a) + (a.has_actor ? per : 0);
 }
 
-int mdqn_train_blocks(const HeadArgs& a) { return mdqn_learn_blocks(a.B); }
-
 void launch_mdqn_head(const HeadArgs& a, hipStream_t st) {
   const size_t lds = mdqn_head_lds_bytes(a);
   if (a.infer) {

@@ -248,8 +248,6 @@ size_t qr_head_lds_bytes(const HeadArgs& a) {
   return qr_infer_q_bytes(a) + (a.has_actor ? per : 0);
 }
 
-int qr_train_blocks(const HeadArgs& a) { return qr_learn_blocks(a.B); }
-
 void launch_qr_head(const HeadArgs& a, hipStream_t st) {
   const size_t lds = qr_head_lds_bytes(a);
   if (a.infer) {

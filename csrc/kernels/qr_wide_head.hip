@@ -279,8 +279,6 @@ size_t qr_wide_head_lds_bytes(const HeadArgs& a) {
   return qrw_infer_q_bytes(a) + (a.has_actor ? per : 0);
 }
 
-int qr_wide_train_blocks(const HeadArgs& a) { return qrw_learn_blocks(a.B); }
-
 void launch_qr_wide_head(const HeadArgs& a, hipStream_t st) {
   const size_t lds = qr_wide_head_lds_bytes(a);
   if (a.infer) {

@@ -378,8 +378,6 @@ size_t c51_head_lds_bytes(const HeadArgs& a) {
   return a.has_actor && a.actor.tsum != nullptr && n < sizeof(SumtreeLds) ? sizeof(SumtreeLds) : n;
 }
 
-int c51_train_blocks(const HeadArgs& a) { return c51_learn_blocks(a.B); }
-
 void launch_c51_head(const HeadArgs& a, hipStream_t st) {
   const size_t lds = c51_head_lds_bytes(a);
   if (a.infer) {

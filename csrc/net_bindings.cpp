@@ -375,6 +375,51 @@ void fc_head(std::vector<int64_t> in, std::vector<int64_t> w, std::vector<int64_
               "fc_head: shape outside the fused kernel (A <= 18, HID <= 512 and % 64 == 0, E <= 16)");
 }
 
+// What the bindings of the rows heads (the heads that read precomputed output rows [B][KD]:
+// C51, QR-DQN, wide QR-DQN, Munchausen) do not share.
+struct RowsHead {
+  const char* name;   // in "<name> head: ..." and "<name> training: ..."
+  const char* tag;    // in "<tag>: ..." and "<tag> fused acting: ..."
+  const char* rows;   // what a row holds
+  int align;          // bytes every row pointer is a multiple of: 1 or 16
+  bool batch;         // training checks io[0..3]: actions, rewards, dones, gammas
+  bool three;         // training takes exactly 3 learner instances, not 2 or 3
+  size_t (*lds_bytes)(const dqn::HeadArgs&);
+  void (*launch)(const dqn::HeadArgs&, hipStream_t);
+};
+
+// The tail of every rows head binding, after its own scalars are in `a`.
+// qp (training): [loss_parts (one float per learner block), dout16 act_t [B][KD]].
+// lg: the instances' rows; a training launch with fused acting carries one more, the actors'.
+void rows_head(const RowsHead& d, dqn::HeadArgs& a, const std::vector<int64_t>& io, std::vector<int64_t> lg,
+               const std::vector<int64_t>& qp) {
+  TORCH_CHECK(d.lds_bytes(a) <= 160 * 1024, d.name, " head: batch too large for one workgroup's LDS");
+  if (!a.infer) {
+    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, d.name,
+                " training: loss partials, dout16, prio");
+    TORCH_CHECK(!d.batch || (io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0), d.name,
+                " training: actions, rewards, dones, gammas");
+    a.loss_parts = P<float*>(qp[0]);
+    a.dq16 = P<void*>(qp[1]);
+  }
+  const bool al = d.align > 1;
+  if (a.act_E > 0) {
+    TORCH_CHECK(!lg.empty(), d.tag, " fused acting: the actors' ", d.rows);
+    TORCH_CHECK(!al || (lg.back() != 0 && lg.back() % d.align == 0), d.tag, " fused acting: ", d.rows,
+                " 16-byte aligned");
+    a.act_lgi = P<const float*>(lg.back());
+    lg.pop_back();
+  }
+  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 3 || (lg.size() == 2 && !d.three)), d.tag, ": ", d.rows,
+              " of every instance", d.three ? " (online(s), target(s'), target(s))" : "");
+  for (size_t i = 0; i < lg.size(); ++i) {
+    TORCH_CHECK(lg[i] != 0 && lg[i] % d.align == 0, d.tag, al ? ": " : ": null ", d.rows,
+                al ? " non-null, 16-byte aligned" : "");
+    a.lgi[i] = P<const float*>(lg[i]);
+  }
+  d.launch(a, cur_stream());
+}
+
 // C51 head: ints as head_loss; dist = [atoms]; flts = [v_min, v_max]; lg = the instances' logits
 // rows (one igemm over the combined output layer: KD floats per row, rainbow.hip c51_kd)
 void c51_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<double> flts, std::vector<int64_t> h,
@@ -382,32 +427,17 @@ void c51_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<
               std::vector<int64_t> io, std::vector<int64_t> pw, std::vector<int64_t> pwv, std::vector<int64_t> zero,
               std::vector<int64_t> actor, std::vector<double> actor_f, int64_t prof, std::vector<int64_t> lg,
               int64_t act_h, std::vector<int64_t> qp) {
-  // training + actor: fused acting; lg then carries one more entry, the actors' logits.
-  // qp (training): [loss_parts (>= c51_train_blocks floats), dout16 act_t [B][KD]]
   TORCH_CHECK(dist.size() == 1 && flts.size() == 2, "c51 args");
   dqn::HeadArgs a = head_args(ints, h, w, b, wv, bv, io, pw, pwv, zero, actor, actor_f, act_h);
   a.atoms = (int)dist[0]; a.vmin = (float)flts[0]; a.vmax = (float)flts[1];
   TORCH_CHECK(a.atoms >= 2 && a.atoms <= 64, "C51: 2..64 atoms (one wave64 lane per atom)");
   TORCH_CHECK(a.vmax > a.vmin, "C51 support");
-  TORCH_CHECK(c51_head_lds_bytes(a) <= 160 * 1024, "C51 head: batch too large for one workgroup's LDS");
-  if (!a.infer) {
-    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, "C51 training: loss partials, dout16, prio");
-    a.loss_parts = P<float*>(qp[0]);
-    a.dq16 = P<void*>(qp[1]);
-  }
   a.prof = P<int64_t*>(prof);
-  if (a.act_E > 0) {
-    TORCH_CHECK(!lg.empty(), "c51 fused acting: the actors' logits");
-    a.act_lgi = P<const float*>(lg.back());
-    lg.pop_back();
-  }
-  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 2 || lg.size() == 3), "c51: logits of every instance");
-  for (size_t i = 0; i < lg.size(); ++i) a.lgi[i] = P<const float*>(lg[i]);
-  launch_c51_head(a, cur_stream());
+  rows_head({"C51", "c51", "logits", 1, false, false, c51_head_lds_bytes, launch_c51_head}, a, io, lg, qp);
 }
 
-// QR-DQN head (qr_head.hip): the arguments of c51_head with dist = [quantiles], flts = [kappa];
-// lg = the instances' quantile rows (the same combined output layer and row layout)
+// QR-DQN head (qr_head.hip): the arguments of c51_head without prof, dist = [quantiles],
+// flts = [kappa]; lg = the instances' quantile rows (the same combined output layer and row layout)
 void qr_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<double> flts, std::vector<int64_t> h,
              std::vector<int64_t> w, std::vector<int64_t> b, std::vector<int64_t> wv, std::vector<int64_t> bv,
              std::vector<int64_t> io, std::vector<int64_t> pw, std::vector<int64_t> pwv, std::vector<int64_t> zero,
@@ -418,24 +448,7 @@ void qr_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector<d
   a.atoms = (int)dist[0]; a.delta = (float)flts[0];
   TORCH_CHECK(a.atoms >= 2 && a.atoms <= 64, "QR-DQN: 2..64 quantiles (one wave64 lane per quantile)");
   TORCH_CHECK(a.delta > 0.f, "QR-DQN: kappa > 0");
-  TORCH_CHECK(qr_head_lds_bytes(a) <= 160 * 1024, "QR head: batch too large for one workgroup's LDS");
-  if (!a.infer) {
-    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, "QR training: loss partials, dout16, prio");
-    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0, "QR training: actions, rewards, dones, gammas");
-    a.loss_parts = P<float*>(qp[0]);
-    a.dq16 = P<void*>(qp[1]);
-  }
-  if (a.act_E > 0) {
-    TORCH_CHECK(!lg.empty(), "qr fused acting: the actors' quantile rows");
-    a.act_lgi = P<const float*>(lg.back());
-    lg.pop_back();
-  }
-  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 2 || lg.size() == 3), "qr: quantile rows of every instance");
-  for (size_t i = 0; i < lg.size(); ++i) {
-    TORCH_CHECK(lg[i] != 0, "qr: null quantile rows");
-    a.lgi[i] = P<const float*>(lg[i]);
-  }
-  launch_qr_head(a, cur_stream());
+  rows_head({"QR", "qr", "quantile rows", 1, true, false, qr_head_lds_bytes, launch_qr_head}, a, io, lg, qp);
 }
 
 // Wide QR-DQN head (qr_wide_head.hip): the arguments of qr_head, for 64 < quantiles <= 256 with
@@ -451,25 +464,8 @@ void qr_wide_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vec
   TORCH_CHECK(a.atoms >= 68 && a.atoms <= 256 && a.atoms % 4 == 0,
               "wide QR-DQN: 68..256 quantiles, a multiple of 4 (four quantiles per 16-byte load), got ", a.atoms);
   TORCH_CHECK(a.delta > 0.f, "wide QR-DQN: kappa > 0");
-  TORCH_CHECK(qr_wide_head_lds_bytes(a) <= 160 * 1024, "wide QR head: batch too large for one workgroup's LDS");
-  if (!a.infer) {
-    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0, "wide QR training: loss partials, dout16, prio");
-    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0, "wide QR training: actions, rewards, dones, gammas");
-    a.loss_parts = P<float*>(qp[0]);
-    a.dq16 = P<void*>(qp[1]);
-  }
-  if (a.act_E > 0) {
-    TORCH_CHECK(!lg.empty(), "wide qr fused acting: the actors' quantile rows");
-    TORCH_CHECK(lg.back() != 0 && lg.back() % 16 == 0, "wide qr fused acting: quantile rows 16-byte aligned");
-    a.act_lgi = P<const float*>(lg.back());
-    lg.pop_back();
-  }
-  TORCH_CHECK(a.infer ? lg.size() == 1 : (lg.size() == 2 || lg.size() == 3), "wide qr: quantile rows of every instance");
-  for (size_t i = 0; i < lg.size(); ++i) {
-    TORCH_CHECK(lg[i] != 0 && lg[i] % 16 == 0, "wide qr: quantile rows non-null, 16-byte aligned");
-    a.lgi[i] = P<const float*>(lg[i]);
-  }
-  launch_qr_wide_head(a, cur_stream());
+  rows_head({"wide QR", "wide qr", "quantile rows", 16, true, false, qr_wide_head_lds_bytes, launch_qr_wide_head}, a,
+            io, lg, qp);
 }
 
 // Munchausen-DQN head (mdqn_head.hip): the arguments of qr_head with dist = [1] (one output per
@@ -489,26 +485,7 @@ void mdqn_head(std::vector<int64_t> ints, std::vector<int64_t> dist, std::vector
   TORCH_CHECK(a.m_tau > 0.f, "Munchausen head: tau > 0");
   TORCH_CHECK(a.m_clip < 0.f, "Munchausen head: clip < 0");
   TORCH_CHECK(!a.huber || a.delta > 0.f, "Munchausen head: Huber delta > 0");
-  TORCH_CHECK(mdqn_head_lds_bytes(a) <= 160 * 1024, "Munchausen head: batch too large for one workgroup's LDS");
-  if (!a.infer) {
-    TORCH_CHECK(qp.size() == 2 && qp[0] != 0 && qp[1] != 0 && io[6] != 0,
-                "Munchausen training: loss partials, dout16, prio");
-    TORCH_CHECK(io[0] != 0 && io[1] != 0 && io[2] != 0 && io[3] != 0,
-                "Munchausen training: actions, rewards, dones, gammas");
-    a.loss_parts = P<float*>(qp[0]);
-    a.dq16 = P<void*>(qp[1]);
-  }
-  if (a.act_E > 0) {
-    TORCH_CHECK(!lg.empty(), "mdqn fused acting: the actors' output rows");
-    a.act_lgi = P<const float*>(lg.back());
-    lg.pop_back();
-  }
-  TORCH_CHECK(lg.size() == (a.infer ? 1u : 3u), "mdqn: output rows of every instance (online(s), target(s'), target(s))");
-  for (size_t i = 0; i < lg.size(); ++i) {
-    TORCH_CHECK(lg[i] != 0, "mdqn: null output rows");
-    a.lgi[i] = P<const float*>(lg[i]);
-  }
-  launch_mdqn_head(a, cur_stream());
+  rows_head({"Munchausen", "mdqn", "output rows", 1, true, true, mdqn_head_lds_bytes, launch_mdqn_head}, a, io, lg, qp);
 }
 
 void noisy_mix(int64_t flat, int64_t eff, int64_t noise, int64_t jobs, int64_t njobs, int64_t max_elems) {

@@ -106,6 +106,12 @@ class _Pending:
 _StepFlags = namedtuple('_StepFlags', 'split gnoise noisy defer dwg det chain zero_in_head')
 
 
+# a head that reads precomputed output rows [B][KD] (``HipExecutor.rows_head``). word: its name in
+# messages, fn: its extension function, dist / flts: that function's per-head lists, prof: it takes
+# the phase-stamp buffer, per_block: samples per learner block (one loss partial each, at most 64)
+_RowsHead = namedtuple('_RowsHead', 'word fn dist flts prof per_block')
+
+
 def _frag_elems(K, N):
     return ((K + 31) // 32) * ((N + 15) // 16) * 512
 
@@ -149,6 +155,16 @@ class HipExecutor:
             from ..models.executor import check_munchausen
             check_munchausen(arch, double_dqn, *self.mdqn)
         self.rows = self.dist or self.mdqn is not None      # the head reads precomputed output rows
+        self.rows_head = None                  # that head, resolved once: _head launches it, _loss_parts counts
+        if self.mdqn is not None:
+            self.rows_head = _RowsHead('Munchausen', 'qnet_mdqn_head', [1], list(self.mdqn) + [self.delta], False, 8)
+        elif self.dist and self.quantile:      # beyond 64 quantiles the wide head: one sample per block at a time
+            wide = self.atoms > 64
+            self.rows_head = _RowsHead('QR-DQN', 'qnet_qr_wide_head' if wide else 'qnet_qr_head', [self.atoms],
+                                       [float(arch.kappa)], False, 1 if wide else 8)
+        elif self.dist:
+            self.rows_head = _RowsHead('C51', 'qnet_c51_head', [self.atoms], [float(arch.v_min), float(arch.v_max)],
+                                       True, 8)
         self.NO = self.A * self.atoms          # output-layer width (advantage / plain head)
         self.noisy = arch.noisy
         self._eff: Dict[int, torch.Tensor] = {}
@@ -913,12 +929,9 @@ class HipExecutor:
         return {'loss_parts': torch.zeros(64, **f32), 'dq16': torch.zeros(B * width, dtype=self.act_dtype, device=dev)}
 
     def _loss_parts(self, B):
-        """Loss partials the head launch writes: one per 16-sample tile (scalar) or per C51
-        learner block (8 samples each, at most 64 blocks; the wide QR-DQN head: one sample per
-        block at a time, at most 64 blocks)."""
-        if self.quantile and self.atoms > 64:
-            return min(B, 64)
-        return min((B + 7) // 8, 64) if self.rows else (B + 15) // 16
+        """Loss partials the head launch writes: one per 16-sample tile (scalar) or per learner
+        block of the rows head (at most 64 blocks)."""
+        return min(-(-B // self.rows_head.per_block), 64) if self.rows else (B + 15) // 16
 
     # ------------------------------------------------------------ forward
     @property
@@ -1125,22 +1138,13 @@ class HipExecutor:
             else:
                 lg = self._c51_logits(hs, pw, pwv, B, dev)
             qp = [ws['loss_parts'].data_ptr(), ws['dq16'].data_ptr()] if not ints[5] else []
-            if self.mdqn is not None:
-                if self.head_prof is not None:
-                    raise RuntimeError('head_prof: the Munchausen head writes no phase stamps (C51 and scalar heads do)')
-                self.ext.qnet_mdqn_head(ints, [1], list(self.mdqn) + [self.delta], hs, w, b, wv, bv, io, [], [],
-                                        zero, actor, actor_f, lg, act_h, qp)
-                return
-            if self.quantile:
-                if self.head_prof is not None:
-                    raise RuntimeError('head_prof: the QR-DQN head writes no phase stamps (C51 and scalar heads do)')
-                head = self.ext.qnet_qr_wide_head if self.atoms > 64 else self.ext.qnet_qr_head
-                head(ints, [self.atoms], [float(self.arch.kappa)], hs, w, b, wv, bv, io, [], [],
-                     zero, actor, actor_f, lg, act_h, qp)
-                return
-            prof = self.head_prof.data_ptr() if self.head_prof is not None and not ints[5] else 0
-            self.ext.qnet_c51_head(ints, [self.atoms], [float(self.arch.v_min), float(self.arch.v_max)], hs, w, b,
-                                   wv, bv, io, [], [], zero, actor, actor_f, prof, lg, act_h, qp)
+            hd = self.rows_head
+            if self.head_prof is not None and not hd.prof:
+                raise RuntimeError('head_prof: the %s head writes no phase stamps (C51 and scalar heads do)' % hd.word)
+            # (positional: the C51 binding takes prof between actor_f and lg, the others have no such slot)
+            prof = [self.head_prof.data_ptr() if self.head_prof is not None and not ints[5] else 0] if hd.prof else []
+            getattr(self.ext, hd.fn)(ints, hd.dist, hd.flts, hs, w, b, wv, bv, io, [], [], zero, actor, actor_f, *prof,
+                                     lg, act_h, qp)
         else:
             prof = self.head_prof.data_ptr() if self.head_prof is not None else 0
             self.ext.qnet_head_loss(ints, [self.delta], hs, w, b, wv, bv, io, pw, pwv,

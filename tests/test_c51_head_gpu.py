@@ -40,25 +40,16 @@ import numpy as np
 import pytest
 import torch
 
+import head_ref as hr
+from head_ref import DEV, HID, PAD_IN, dims as _dims, ext as _ext
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device('cuda', 0)
-SENT = -4096.0                 # exact in bf16 / fp16 / fp32, below anything the kernels can write
-PAD_IN = 1e9
-HID = 128                      # (unused by the C51 kernels; the binding wants a multiple of 128)
-# variant -> (act_t as HipExecutor.act_dtype maps it, storage rounding step, kLossScale)
-BUILDS = {'': (torch.bfloat16, 2.0 ** -8, 1.0), 'f16': (torch.float16, 2.0 ** -11, 1024.0),
-          'f32': (torch.float32, 0.0, 1.0)}
+FN = 'qnet_c51_head'
 S10 = (-10.0, 10.0)
 
 
-def _dims(A, N, dueling):
-    NO = A * N
-    VO = (NO + 31) // 32 * 32
-    return NO, VO, VO + ((N + 31) // 32 * 32 if dueling else 0)
-
-
 def _blocks(B):
-    return min((B + 7) // 8, 64)
+    return min((B + 7) // 8, 64)   # eight samples (one per wave) per learner block
 
 
 # ------------------------------------------------------------------ inputs (CPU, seeded)
@@ -85,26 +76,15 @@ def _inputs(B, A, N, dueling, double, wmode, sup, seed):
     edges = [(v_max + 1.0, 1.0, 0.99), (v_min - 1.0, 1.0, 0.99), (v_max, 1.0, 0.99), (0.0, 1.0, 0.99),
              (float(zf[N // 3]), 1.0, 0.99), (0.0, 0.0, 1.0), (dz / 2, 0.0, 1.0),
              (v_min + 0.3 * (v_max - v_min), 0.0, 0.0)]
-    rew = torch.randn(B, generator=g) * (v_max - v_min) / 4
-    done = (torch.rand(B, generator=g) < 0.2).float()
-    gam = torch.tensor([0.99 ** (1 + i % 3) for i in range(B)])
-    for i, (r, d, gm) in enumerate(edges[:B]):
-        rew[i], done[i], gam[i] = r, d, gm
-    act = torch.randint(0, A, (B,), generator=g, dtype=torch.int32)
-    act[0] = A - 1
-    act[B - 1] = 0
-    wts, zrow = None, None
-    if wmode != 'none':
-        wts = torch.rand(B, generator=g) + 0.5
-        if wmode == 'zero':
-            zrow = 10 if B > 10 else B - 1
-            wts[zrow] = 0.0
+    rew, done, gam = hr.draw_transitions(g, B, edges, (v_max - v_min) / 4)
+    act = hr.draw_actions(g, B, A)
+    wts, zrow = hr.draw_weights(g, B, wmode)
     rows = torch.full((3, B, KD), PAD_IN)
     rows[:, :, :NO] = x.reshape(3, B, NO)
     if dueling:
         rows[:, :, VO:VO + N] = v
-    return dict(B=B, A=A, N=N, dueling=dueling, double=double, sup=sup, rows=rows.float(), rew=rew.float(),
-                done=done, gam=gam.float(), act=act, wts=None if wts is None else wts.float(), tie=tie, zrow=zrow)
+    return dict(B=B, A=A, N=N, dueling=dueling, double=double, sup=sup, rows=rows.float(), rew=rew, done=done,
+                gam=gam, act=act, wts=wts, tie=tie, zrow=zrow)
 
 
 # ------------------------------------------------------------------ float64 reference
@@ -171,70 +151,17 @@ def _dout_ref(c, ref):
 
 
 # ------------------------------------------------------------------ launches
-def _ext(variant):
-    from dist_dqn_amd.ops import _ext as loader
-    return loader.load(required=True, variant=variant)
-
-
-def _train(ext, c, act_t):
-    B, A, N = c['B'], c['A'], c['N']
-    _, _, KD = _dims(A, N, c['dueling'])
-    t = {k: c[k].to(DEV).contiguous() for k in ('rows', 'rew', 'done', 'gam', 'act')}
-    wts = None if c['wts'] is None else c['wts'].to(DEV)
-    dout = torch.full(((B + 8) * KD,), SENT, dtype=act_t, device=DEV)
-    prio = torch.full((B + 8,), SENT, dtype=torch.float32, device=DEV)
-    parts = torch.full((72,), SENT, dtype=torch.float32, device=DEV)
-    io = [t['act'].data_ptr(), t['rew'].data_ptr(), t['done'].data_ptr(), t['gam'].data_ptr(),
-          0 if wts is None else wts.data_ptr(), 0, prio.data_ptr()] + [0] * 6
-    lg = [t['rows'][i].data_ptr() for i in range(3 if c['double'] else 2)]
-    ext.qnet_c51_head([B, A, HID, int(c['dueling']), 0, 0], [N], [c['sup'][0], c['sup'][1]], [], [], [], [], [], io,
-                      [], [], [], [], [], 0, lg, 0, [parts.data_ptr(), dout.data_ptr()])
-    torch.cuda.synchronize()
-    return dout.cpu(), prio.cpu(), parts.cpu()
-
-
 _ratios = {}
 
 
 def _check_train(variant, c):
-    act_t, ulp, scale = BUILDS[variant]
-    B, A, N = c['B'], c['A'], c['N']
-    NO, VO, KD = _dims(A, N, c['dueling'])
     ref = _reference(c)
-    skip = ref['skip']
-    assert int(skip.sum()) * 16 <= B, ('near-ties in the reference: pick another seed', np.nonzero(skip)[0])
-    keep = ~skip
-    ext = _ext(variant)
-    dout, prio, parts = _train(ext, c, act_t)
-    dout2, prio2, _ = _train(ext, c, act_t)
-    assert torch.equal(prio, prio2) and torch.equal(dout.view(torch.uint8), dout2.view(torch.uint8)), 'repeatability'
-    # layout and write coverage
-    d = dout.double().view(B + 8, KD).numpy()
     g, mask = _dout_ref(c, ref)
-    assert (d[:B][:, ~mask] == SENT).all(), 'a pad column was written'
-    assert (d[B:] == SENT).all() and (prio[B:] == SENT).all(), 'a row beyond B was written'
-    assert (d[:B][:, mask] != SENT).all() and (prio[:B] != SENT).all(), 'a logits / value column was left unwritten'
-    nb = _blocks(B)
-    assert (parts[nb:] == SENT).all() and (parts[:nb] != SENT).all(), 'loss partials'
-    # priorities (unweighted cross-entropy) and the loss (the fc dgrad launch's aux duty: sum / B)
-    pk = prio[:B].double().numpy()
-    print('ce: max |err| %.3g at |ce| up to %.3g' % (np.abs(pk - ref['ce'])[keep].max(), ref['ce'].max()))
-    np.testing.assert_allclose(pk[keep], ref['ce'][keep], rtol=1e-4, atol=1e-5)
-    loss_ref = float((ref['w'] * np.where(keep, ref['ce'], pk)).sum() / B)
-    np.testing.assert_allclose(float(parts[:nb].double().sum()) / B, loss_ref, rtol=1e-4, atol=1e-5)
-    # dL/dlogits rows
-    wb = (ref['w'] / B)[:, None]
-    want = g * wb * scale
-    bound = ulp * np.abs(want) + (1e-4 * np.abs(g) + 1e-6) * wb * scale
-    err = np.abs(d[:B] - want)
-    sel = keep[:, None] & mask[None, :]
-    ratio = np.where(sel & (bound > 0), err / np.where(bound > 0, bound, 1.0), 0.0)
-    _ratios[variant] = max(_ratios.get(variant, 0.0), float(ratio.max()))
-    print('dout16 %r: max err / bound %.3f (build so far %.3f)' % (variant, ratio.max(), _ratios[variant]))
-    bad = sel & (err > bound)
-    assert not bad.any(), (int(bad.sum()), [(int(b), int(k), d[b, k], want[b, k]) for b, k in np.argwhere(bad)[:5]])
-    if c['zrow'] is not None:
-        assert (d[c['zrow']][mask] == 0.0).all(), 'zero-weight row'
+    call = FN, [c['B'], c['A'], HID, int(c['dueling']), 0, 0], [c['N']], [c['sup'][0], c['sup'][1]]
+    # (priorities: the unweighted cross-entropy, which is the per-sample loss too)
+    hr.check_train(variant, c, call, 3 if c['double'] else 2, mask.size, _blocks(c['B']),
+                   dict(g=g, t=1e-4 * np.abs(g) + 1e-6, mask=mask, prio=ref['ce'], per=ref['ce'], w=ref['w'],
+                        skip=ref['skip']), ('ce', 'ce', 'a logits / value column'), _ratios)
 
 
 TRAIN_CASES = [
@@ -250,6 +177,7 @@ TRAIN_CASES = [
     (24, 6, 21, 0, 1, 'rand', (0.0, 200.0)), (24, 6, 62, 1, 1, 'rand', (-1.0, 1.0)),
     (24, 4, 30, 0, 0, 'none', (-21.0, 21.0)),
 ]
+OTHER_BUILDS_CASE = (24, 6, 51, 1, 1, 'zero', S10)
 
 
 def _seed(B, A, N, dueling, double):
@@ -258,24 +186,24 @@ def _seed(B, A, N, dueling, double):
     return 1000 * A + 10 * N + B + 2 * dueling + double
 
 
+def _make(case):
+    B, A, N, dueling, double, wmode, sup = case
+    return _inputs(B, A, N, dueling, double, wmode, sup, _seed(B, A, N, dueling, double))
+
+
 @pytest.mark.parametrize('B,A,N,dueling,double,wmode,sup', TRAIN_CASES)
 def test_c51_train_matches_float64(B, A, N, dueling, double, wmode, sup):
-    _check_train('', _inputs(B, A, N, dueling, double, wmode, sup, _seed(B, A, N, dueling, double)))
+    _check_train('', _make((B, A, N, dueling, double, wmode, sup)))
 
 
 @pytest.mark.parametrize('variant', ['f16', 'f32'])
 def test_c51_train_other_builds(variant):
-    _check_train(variant, _inputs(24, 6, 51, 1, 1, 'zero', S10, _seed(24, 6, 51, 1, 1)))
+    _check_train(variant, _make(OTHER_BUILDS_CASE))
 
 
 # ------------------------------------------------------------------ inference kernel
-def _infer(ext, rows, B, A, N, dueling, sup):
-    r = rows.to(DEV).contiguous()
-    q = torch.full((B * A + 8,), float('nan'), dtype=torch.float32, device=DEV)
-    ext.qnet_c51_head([B, A, HID, int(dueling), 0, 1], [N], [sup[0], sup[1]], [], [], [], [], [],
-                      [0] * 7 + [q.data_ptr()] + [0] * 5, [], [], [], [], [], 0, [r.data_ptr()], 0, [])
-    torch.cuda.synchronize()
-    return q.cpu()
+def _infer(rows, B, A, N, dueling, sup):
+    return hr.infer(_ext(''), FN, [N], [sup[0], sup[1]], rows, B, A, dueling)
 
 
 INFER_POINTS = [(2, 51, 0), (4, 51, 1), (5, 51, 0), (8, 51, 1), (9, 51, 1), (18, 51, 1), (19, 51, 0),
@@ -287,21 +215,19 @@ INFER_POINTS = [(2, 51, 0), (4, 51, 1), (5, 51, 0), (8, 51, 1), (9, 51, 1), (18,
 def test_c51_infer_matches_float64(A, N, dueling, B):
     """q_values' kernel; B = 32 with 18 actions of 51 atoms takes 126,336 bytes of dynamic LDS."""
     c = _inputs(B, A, N, dueling, False, 'none', S10, _seed(B, A, N, dueling, 0))
-    q = _infer(_ext(''), c['rows'][0], B, A, N, dueling, S10)
-    assert torch.isnan(q[B * A:]).all(), 'written beyond [B][A]'
-    assert not torch.isnan(q[:B * A]).any(), 'q_out left unwritten'
+    q = _infer(c['rows'][0], B, A, N, dueling, S10)
     _, p = _dist64(c['rows'][0], A, N, dueling)
     ref = (p * _support(S10, N)[0]).sum(-1)
-    np.testing.assert_allclose(q[:B * A].double().numpy().reshape(B, A), ref, rtol=1e-4, atol=1e-5 * 10.0)
+    np.testing.assert_allclose(q, ref, rtol=1e-4, atol=1e-5 * 10.0)
 
 
 def test_c51_infer_other_support():
     B, A, N, sup = 32, 6, 62, (-1.0, 1.0)
     c = _inputs(B, A, N, 1, False, 'none', sup, 7)
-    q = _infer(_ext(''), c['rows'][0], B, A, N, 1, sup)
+    q = _infer(c['rows'][0], B, A, N, 1, sup)
     _, p = _dist64(c['rows'][0], A, N, 1)
     ref = (p * _support(sup, N)[0]).sum(-1)
-    np.testing.assert_allclose(q[:B * A].double().numpy().reshape(B, A), ref, rtol=1e-4, atol=1e-5 * 1.0)
+    np.testing.assert_allclose(q, ref, rtol=1e-4, atol=1e-5 * 1.0)
 
 
 def test_c51_infer_refuses_rows_beyond_lds():

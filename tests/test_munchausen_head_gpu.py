@@ -62,15 +62,11 @@ import numpy as np
 import pytest
 import torch
 
-DEV = torch.device('cuda', 0)
-SENT = -4096.0                 # exact in bf16 / fp16 / fp32, below anything the kernels can write
-PAD_IN = 1e9
-HID = 128                      # (unused by these kernels; the binding wants a multiple of 128)
-E24 = 2.0 ** -24
+import head_ref as hr
+from head_ref import DEV, E24, HID, PAD_IN, ext as _ext
+
+FN = 'qnet_mdqn_head'
 VO = 32
-# variant -> (act_t as HipExecutor.act_dtype maps it, storage rounding step, kLossScale)
-BUILDS = {'': (torch.bfloat16, 2.0 ** -8, 1.0), 'f16': (torch.float16, 2.0 ** -11, 1024.0),
-          'f32': (torch.float32, 0.0, 1.0)}
 
 
 def _kd(dueling):
@@ -87,9 +83,7 @@ def _inputs(B, A, dueling, huber, delta, wmode, tau, alpha, seed, clip=-1.0):
     KD = _kd(dueling)
     x = torch.randn(3, B, A, generator=g) * 3.0
     v = torch.randn(3, B, generator=g) * 3.0
-    act = torch.randint(0, A, (B,), generator=g, dtype=torch.int32)
-    act[0] = A - 1
-    act[B - 1] = 0
+    act = hr.draw_actions(g, B, A)
     tie = None
     if B > 8:
         x[:, 8] *= 30.0
@@ -103,24 +97,14 @@ def _inputs(B, A, dueling, huber, delta, wmode, tau, alpha, seed, clip=-1.0):
             x[inst, 9, i2] = x[inst, 9, i1]
         act[9] = i2
         tie = (9, i1, i2)
-    rew = torch.randn(B, generator=g)
-    done = (torch.rand(B, generator=g) < 0.2).float()
-    gam = torch.tensor([0.99 ** (1 + i % 3) for i in range(B)])
-    for i, (r, d, gm) in enumerate([(1.0, 1.0, 0.99), (0.5, 0.0, 0.0)][:B]):
-        rew[i], done[i], gam[i] = r, d, gm
-    wts, zrow = None, None
-    if wmode != 'none':
-        wts = torch.rand(B, generator=g) + 0.5
-        if wmode == 'zero':
-            zrow = 10 if B > 10 else B - 1
-            wts[zrow] = 0.0
+    rew, done, gam = hr.draw_transitions(g, B, [(1.0, 1.0, 0.99), (0.5, 0.0, 0.0)])
+    wts, zrow = hr.draw_weights(g, B, wmode)
     rows = torch.full((3, B, KD), PAD_IN)
     rows[:, :, :A] = x
     if dueling:
         rows[:, :, VO] = v
     return dict(B=B, A=A, dueling=dueling, huber=huber, delta=delta, tau=tau, alpha=alpha, clip=clip,
-                rows=rows.float(), rew=rew.float(), done=done, gam=gam.float(), act=act,
-                wts=None if wts is None else wts.float(), tie=tie, zrow=zrow)
+                rows=rows.float(), rew=rew, done=done, gam=gam, act=act, wts=wts, tie=tie, zrow=zrow)
 
 
 # ------------------------------------------------------------------ float64 reference
@@ -194,74 +178,21 @@ def _t_g(c, ref):
 
 
 # ------------------------------------------------------------------ launches
-def _ext(variant):
-    from dist_dqn_amd.ops import _ext as loader
-    return loader.load(required=True, variant=variant)
-
-
-def _flts(c):
-    return [float(c['alpha']), float(c['tau']), float(c['clip']), float(c['delta'])]
-
-
-def _train(ext, c, act_t):
-    B, A = c['B'], c['A']
-    KD = _kd(c['dueling'])
-    t = {k: c[k].to(DEV).contiguous() for k in ('rows', 'rew', 'done', 'gam', 'act')}
-    wts = None if c['wts'] is None else c['wts'].to(DEV)
-    dout = torch.full(((B + 8) * KD,), SENT, dtype=act_t, device=DEV)
-    prio = torch.full((B + 8,), SENT, dtype=torch.float32, device=DEV)
-    parts = torch.full((72,), SENT, dtype=torch.float32, device=DEV)
-    io = [t['act'].data_ptr(), t['rew'].data_ptr(), t['done'].data_ptr(), t['gam'].data_ptr(),
-          0 if wts is None else wts.data_ptr(), 0, prio.data_ptr()] + [0] * 6
-    lg = [t['rows'][i].data_ptr() for i in range(3)]
-    ext.qnet_mdqn_head([B, A, HID, int(c['dueling']), int(c['huber']), 0], [1], _flts(c), [], [], [], [], [], io,
-                       [], [], [], [], [], lg, 0, [parts.data_ptr(), dout.data_ptr()])
-    torch.cuda.synchronize()
-    return dout.cpu(), prio.cpu(), parts.cpu()
-
-
 _ratios = {}
 
 
 def _check_train(variant, c):
-    act_t, ulp, scale = BUILDS[variant]
     B, A = c['B'], c['A']
-    KD = _kd(c['dueling'])
     ref = _reference(c)
-    ext = _ext(variant)
-    dout, prio, parts = _train(ext, c, act_t)
-    dout2, prio2, parts2 = _train(ext, c, act_t)
-    assert torch.equal(prio, prio2) and torch.equal(dout.view(torch.uint8), dout2.view(torch.uint8)) \
-        and torch.equal(parts, parts2), 'repeatability'
-    # layout and write coverage
-    d = dout.double().view(B + 8, KD).numpy()
     g, cf, mask = _dout_ref(c, ref)
-    assert (d[:B][:, ~mask] == SENT).all(), 'a pad column was written'
-    assert (d[B:] == SENT).all() and (prio[B:] == SENT).all(), 'a row beyond B was written'
-    assert (d[:B][:, mask] != SENT).all() and (prio[:B] != SENT).all(), 'a Q / value column was left unwritten'
-    nb = _blocks(B)
-    assert (parts[nb:] == SENT).all() and (parts[:nb] != SENT).all(), 'loss partials'
-    assert np.isfinite(d[:B][:, mask]).all() and torch.isfinite(prio[:B]).all() and torch.isfinite(parts[:nb]).all()
-    # priorities |d| and the loss (the fc dgrad launch's aux duty: sum / B)
-    pk = prio[:B].double().numpy()
-    print('prio: max |err| %.3g at |d| up to %.3g' % (np.abs(pk - ref['ad']).max(), ref['ad'].max()))
-    np.testing.assert_allclose(pk, ref['ad'], rtol=1e-4, atol=1e-5)
-    loss_ref = float((ref['w'] * ref['per']).sum() / B)
-    np.testing.assert_allclose(float(parts[:nb].double().sum()) / B, loss_ref, rtol=1e-4, atol=1e-5)
-    # dL/dQ rows: every written element of every row is compared (nothing is excluded)
-    wb = (ref['w'] / B)[:, None]
-    want = g * wb * scale
-    bound = (ulp + 5 * E24) * np.abs(want) + _t_g(c, ref)[:, None] * cf * wb * scale
-    err = np.abs(d[:B] - want)
-    sel = np.broadcast_to(mask[None, :], err.shape)            # (no row mask: nothing is excluded)
-    assert int(sel.sum()) == B * (A + int(c['dueling'])), 'every written element of every row is compared'
-    ratio = np.where(sel & (bound > 0), err / np.where(bound > 0, bound, 1.0), 0.0)
-    _ratios[variant] = max(_ratios.get(variant, 0.0), float(ratio.max()))
-    print('dout16 %r: max err / bound %.3f (build so far %.3f)' % (variant, ratio.max(), _ratios[variant]))
-    bad = sel & (err > bound)
-    assert not bad.any(), (int(bad.sum()), [(int(b), int(k), d[b, k], want[b, k]) for b, k in np.argwhere(bad)[:5]])
-    if c['zrow'] is not None:
-        assert (d[c['zrow']][mask] == 0.0).all(), 'zero-weight row'
+    # no row is left out (skip=None), so every written element of every row is compared
+    assert int(mask.sum()) == A + int(c['dueling'])
+    call = (FN, [B, A, HID, int(c['dueling']), int(c['huber']), 0], [1],
+            [float(c['alpha']), float(c['tau']), float(c['clip']), float(c['delta'])])
+    # rel = 5 e: the roundings of w / B, its products with g, the loss scale and the dueling coefficient
+    hr.check_train(variant, c, call, 3, _kd(c['dueling']), _blocks(B),
+                   dict(g=g, t=_t_g(c, ref)[:, None] * cf, mask=mask, prio=ref['ad'], per=ref['per'], w=ref['w'],
+                        skip=None), ('prio', 'd', 'a Q / value column'), _ratios, rel=5 * E24)
     # what the scaled row is there for: the clip at l0 is active and soft sits at the maximum
     if B > 8:
         assert ref['lp'].min() < c['clip'] and (ref['lp'] <= 0).all()
@@ -334,15 +265,6 @@ def test_mdqn_head_refuses_bad_arguments():
 
 
 # ------------------------------------------------------------------ inference kernel
-def _infer(ext, rows, B, A, dueling):
-    r = rows.to(DEV).contiguous()
-    q = torch.full((B * A + 8,), float('nan'), dtype=torch.float32, device=DEV)
-    ext.qnet_mdqn_head([B, A, HID, int(dueling), 0, 1], [1], [0.9, 0.03, -1.0, 1.0], [], [], [], [], [],
-                       [0] * 7 + [q.data_ptr()] + [0] * 5, [], [], [], [], [], [r.data_ptr()], 0, [])
-    torch.cuda.synchronize()
-    return q.cpu()
-
-
 INFER_POINTS = [(2, 0), (4, 1), (5, 0), (8, 1), (9, 1), (16, 1), (17, 1), (18, 1), (19, 0), (32, 1), (32, 0)]
 
 
@@ -353,11 +275,9 @@ def test_mdqn_infer_matches_float64(A, dueling, B):
     """q_values' kernel: the dueling combine (B = 513: more rows than the block's 64 row groups
     take in eight passes)."""
     c = _inputs(B, A, dueling, 0, 1.0, 'none', 0.03, 0.9, _seed(B, A, dueling, 0))
-    q = _infer(_ext(''), c['rows'][0], B, A, dueling)
-    assert torch.isnan(q[B * A:]).all(), 'written beyond [B][A]'
-    assert not torch.isnan(q[:B * A]).any(), 'q_out left unwritten'
+    q = hr.infer(_ext(''), FN, [1], [0.9, 0.03, -1.0, 1.0], c['rows'][0], B, A, dueling)
     q64, mag = _q64(c['rows'][0], A, dueling)
-    err = np.abs(q[:B * A].double().numpy().reshape(B, A) - q64)
+    err = np.abs(q - q64)
     bound = (11 if dueling else 0) * E24 * mag[:, None]
     print('q: max err / (11 e M) %.3f' % (err / (11 * E24 * mag[:, None])).max())
     assert (err <= bound).all(), float((err / (11 * E24 * mag[:, None])).max())

@@ -2,7 +2,7 @@
 (``qr_infer_kernel`` with the fused actor step, what ``DeviceActor.step()`` / ``act_fused`` run) and
 the acting blocks of the training launch (``qr_act_env_block``, one block per env).
 
-* On synthetic quantile rows (the harness of test_qr_head_gpu.py) with epsilon = 0, every env's
+* On synthetic quantile rows (the inputs of test_qr_head_gpu.py, qr_ref.py) with epsilon = 0, every env's
   appended action is the first argmax of the float64 quantile means of its row (dueling combined),
   for both launches; the transition lands at the cursor with the env's frame stack, the next frame
   slot and gamma; cursor, frame counter and ticket advance; with prioritized replay the E new
@@ -22,7 +22,9 @@ import numpy as np
 import pytest
 import torch
 
-from test_qr_head_gpu import DEV, HID, _dims, _ext, _inputs, _quantiles64, _train
+from head_ref import DEV, HID, dims as _dims, ext as _ext
+from qr_ref import inputs as _inputs, quantiles64 as _quantiles64
+from qr_ref import train as _qr_train
 
 pytestmark = pytest.mark.gpu
 CAP = 256
@@ -109,7 +111,7 @@ def test_qr_training_launch_acting_blocks_act_on_the_quantile_means(E, A, N, due
     rows = _inputs(E, A, N, dueling, False, 'none', 1.0, 9000 + 100 * A + N + E)['rows'][0]
     best, skip, _, _ = _greedy64(rows, A, N, dueling)
     ext = _ext('')
-    dout0, prio0, parts0 = _train(ext, c, torch.bfloat16)            # the same launch without acting blocks
+    dout0, prio0, parts0 = _qr_train(ext, 'qnet_qr_head', c, torch.bfloat16)     # the same launch without acting blocks
     rep, actor, args, f = _actor(A, E, per)
     stacks0, f0 = actor.stacks.clone(), int(rep.cursor[1])
     _, _, KD = _dims(A, N, dueling)
